@@ -8,11 +8,18 @@ every rank).  The database (100M Quest transactions, |T|=10, |I|=4, |L|=2000,
 N=1000 items) is generated deterministically per rank and kept resident in HBM
 before timing.  The total work is fixed as N grows, so scaling is "strong".
 
-After the timed steps the reference's own timing window (Main.scala:28-32:
-read + parse D.dat, mine, write freqItemset) is measured on the same database
-written to a D.dat file: once with the file's pages dropped from the page cache
-(posix_fadvise DONTNEED after fsync) and then warm.  Those numbers go into the
-JSON line's "e2e" record (``--e2e off`` skips them).
+A plain run does only what the headline figure needs: it generates the database,
+warms up, times the steps, writes the last step's result if ``--dump-outputs DIR``
+is given and prints the JSON line.  Everything below is measured or checked only
+with ``--full``; in a plain run those fields of the JSON line are null.
+
+``--full``: after the timed steps the reference's own timing window
+(Main.scala:28-32: read + parse D.dat, mine, write freqItemset) is measured on the
+same database written to a D.dat file: once with the file's pages dropped from the
+page cache (posix_fadvise DONTNEED after fsync) and then warm.  Those numbers go
+into the JSON line's "e2e" record (``--e2e off`` skips them).  ``--full`` also adds
+the per-rank diagnostics (one extra untimed run with phase timers), the result's
+digest and its check against the CPU path's, and ``vs_baseline``.
 
 ``vs_baseline`` = this run's itemsets/s over the multi-threaded C++ CPU path of
 the same miner on the same config (BASELINE.md:27: the reference publishes no
@@ -22,6 +29,13 @@ row and counts every level with a column-tiled prefix-shared AND+popcount (its
 "what" field is copied into the JSON line).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config T10I4D100M]
+                    [--dump-outputs DIR] [--full]
+
+``--dump-outputs DIR`` writes what the last timed ``miner.run`` returned (rank 0's
+copy; every rank holds the same result) as float64 ``DIR/<name>.npy``: ``items``
+(rank -> numeric token), ``min_count``, and per level k ``level<k>_itemsets``
+([F_k, k] ranks) and ``level<k>_counts``.  The database depends only on the
+arguments (config, --n-txn, --seed), so two builds can be compared file by file.
 
 ``--gpus N`` > 1 without a torchrun environment re-launches this script under
 ``torch.distributed.run`` with N ranks (one per GPU, RCCL); under torchrun the
@@ -72,12 +86,17 @@ def parse_args(argv=None):
     ap.add_argument("--strategy", choices=["count", "candidate"], default="count",
                     help="count: each rank generates its row shard; candidate: every rank holds all rows")
     ap.add_argument("--e2e", choices=["auto", "on", "off"], default="auto",
-                    help="also time the reference window (read+parse+mine+write) on a D.dat file "
+                    help="with --full: also time the reference window (read+parse+mine+write) on a D.dat file "
                          "(auto: on for file-backed configs)")
     ap.add_argument("--e2e-runs", type=int, default=2, help="warm-cache e2e runs after the cold one")
     ap.add_argument("--workdir", default="", help="where the e2e D.dat is written (default $TMPDIR)")
     ap.add_argument("--no-digest-check", action="store_true",
                     help="report the result digest without failing on a mismatch (timing-only kernel variants)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's result as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: per-rank diagnostics (one extra "
+                         "run), the e2e windows, the digest check and the CPU baseline comparison")
     return ap.parse_args(argv)
 
 
@@ -331,6 +350,38 @@ def _per_rank(args, comm, miner, shard, own_ms, comm_ms, comm_calls, sync) -> li
     return comm.all_gather_object(rec)
 
 
+DUMP_LIMIT = 64 << 20          # bytes of .npy data written by --dump-outputs
+DUMP_SEED = 20240229           # of the row sample taken when a result is larger than DUMP_LIMIT
+
+
+def _dump_outputs(dirname: str, res) -> None:
+    """The MiningResult of the last timed step as float64 DIR/<name>.npy files (ranks,
+    counts <= n_txn and numeric tokens are exact in float64).  A result over DUMP_LIMIT
+    is cut to a fixed, seeded sample of each level's rows (the same rows of both arrays,
+    in their original order), every level by the same fraction."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    try:
+        items = np.array([float(t) for t in res.items], dtype=np.float64)
+    except ValueError:             # dictionary-mode tokens: the rank order itself
+        items = np.arange(len(res.items), dtype=np.float64)
+    out = {"items": items, "min_count": np.array([res.min_count], dtype=np.float64)}
+    total = sum(a.size for a in out.values()) * 8
+    rows_bytes = sum((np.asarray(r).size + np.asarray(c).size) * 8 for r, c in zip(res.levels, res.counts))
+    frac = min(1.0, max(DUMP_LIMIT - total - 4096 * (1 + 2 * len(res.levels)), 0) / max(rows_bytes, 1))
+    rng = np.random.default_rng(DUMP_SEED)
+    for k, (rows, cnt) in enumerate(zip(res.levels, res.counts), 1):
+        rows = np.asarray(rows).reshape(-1, k)
+        cnt = np.asarray(cnt).ravel()
+        if frac < 1.0:
+            keep = np.sort(rng.choice(len(cnt), size=int(len(cnt) * frac), replace=False))
+            rows, cnt = rows[keep], cnt[keep]
+        out[f"level{k}_itemsets"] = rows.astype(np.float64)
+        out[f"level{k}_counts"] = cnt.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main() -> int:
     args = parse_args()
     in_torchrun = "WORLD_SIZE" in os.environ and "RANK" in os.environ
@@ -404,10 +455,12 @@ def main() -> int:
     n_sets = res.n_itemsets
     value = n_sets / (ms_step / 1e3)
     stats = dict(miner.stats)
-    per_rank = _per_rank(args, comm, miner, shard, own_ms, comm_ms, comm_calls, sync)
+    if args.dump_outputs and comm.is_root and res is not None:
+        _dump_outputs(args.dump_outputs, res)
+    per_rank = _per_rank(args, comm, miner, shard, own_ms, comm_ms, comm_calls, sync) if args.full else None
 
     e2e = None
-    want_e2e = args.e2e == "on" or (args.e2e == "auto" and not webdocs and args.strategy == "count")
+    want_e2e = args.full and (args.e2e == "on" or (args.e2e == "auto" and not webdocs and args.strategy == "count"))
     if want_e2e and args.steps > 0:
         del shard
         e2e, _ = _e2e_window(args, comm, n_txn, min_sup, CONFIGS[args.config], cfg, sync)
@@ -416,11 +469,11 @@ def main() -> int:
                   file=sys.stderr)
             return 3
 
-    base = cpu_baseline(args.config, min_sup, n_txn)
+    base = cpu_baseline(args.config, min_sup, n_txn) if args.full else None
     # correctness at benchmark scale (outside the timed region): the result's digest
     # (MiningResult.digest: the set of (itemset, count) in token space) against the C++
     # CPU path's on the same data, when benchmarks/cpu_baselines.json holds one
-    digest = res.digest() if res is not None else None
+    digest = res.digest() if (args.full and res is not None) else None
     want = base.get("digest") if base else None
     digest_ok = None if (want is None or digest is None) else digest == want
     if comm.is_root:
@@ -433,6 +486,7 @@ def main() -> int:
             "backend": comm.backend,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(ms_step, 3),
             "higher_is_better": True,
             "scaling": "strong",

@@ -38,5 +38,5 @@ cd /tmp
 for s in "$@"; do
   t=$(tag "$s")
   FA_TUNE=$(spec "$s") timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt_$t" -o run -- \
-    python3 "$R/bench.py" --config "$CFG" --steps 1 --warmup 1 --e2e off > "$O/kt_$t.log" 2>&1
+    python3 "$R/bench.py" --config "$CFG" --steps 1 --warmup 1 --full --e2e off > "$O/kt_$t.log" 2>&1
 done

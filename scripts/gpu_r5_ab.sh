@@ -22,5 +22,5 @@ done
 cd /tmp
 for v in "$@"; do
   FA_TUNE="$K=$v" timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt_$v" -o run -- \
-    python3 "$R/bench.py" --steps 1 --warmup 1 --e2e off > "$O/kt_$v.log" 2>&1
+    python3 "$R/bench.py" --steps 1 --warmup 1 --full --e2e off > "$O/kt_$v.log" 2>&1
 done

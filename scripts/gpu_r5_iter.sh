@@ -15,4 +15,4 @@ timeout -k 10 300 python bench.py --n-txn 12500000 --steps 40 --warmup 3 --e2e o
 timeout -k 10 400 python bench.py --steps 10 --warmup 2 --e2e off > $O/T10.json 2> $O/T10.err
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt12" -o run -- \
-  python3 "$R/bench.py" --n-txn 12500000 --steps 1 --warmup 1 --e2e off > "$O/kt12.log" 2>&1
+  python3 "$R/bench.py" --n-txn 12500000 --steps 1 --warmup 1 --full --e2e off > "$O/kt12.log" 2>&1

@@ -11,5 +11,5 @@ cd /tmp
 for v in "$@"; do
   if [ "$v" = base ]; then L=""; else L="$R/scripts/microbench/var/libfa_hip_$v.so"; fi
   FA_HIP_LIB="$L" timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt_$v" -o run -- \
-    python3 "$R/bench.py" --n-txn 12500000 --steps 5 --warmup 1 --e2e off > "$O/kt_$v.log" 2>&1
+    python3 "$R/bench.py" --n-txn 12500000 --steps 5 --warmup 1 --full --e2e off > "$O/kt_$v.log" 2>&1
 done

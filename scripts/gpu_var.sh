@@ -15,5 +15,5 @@ ARGS="$ARGS --no-digest-check"
 for v in "$@"; do
   if [ "$v" = base ]; then L=""; else L="$R/scripts/microbench/var/libfa_hip_$v.so"; fi
   FA_HIP_LIB="$L" timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt_${CFG}_$v" -o run -- \
-    python3 "$R/bench.py" $ARGS --e2e off > "$O/kt_${CFG}_$v.log" 2>&1
+    python3 "$R/bench.py" $ARGS --full --e2e off > "$O/kt_${CFG}_$v.log" 2>&1
 done
