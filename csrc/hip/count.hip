@@ -18,6 +18,7 @@
 #include <cstdlib>
 
 #include "fa_hip.h"
+#include "../host/fa_slab.h"
 
 namespace fa {
 
@@ -1454,7 +1455,7 @@ __device__ __forceinline__ void slab_copy_bm(uint4* lds4, int n_used, const uint
 // rank -> slab-row map of the slab build is copied to LDS as u16 (one dependent
 // global load less per rank).
 // ---------------------------------------------------------------------------
-constexpr int kMapLdsMax = 8192;   // plan.cpp fa_slab_map_lds: F1 <= this keeps the map in LDS
+constexpr int kMapLdsMax = kSlabMapMaxF1;   // fa_slab.h: F1 <= this keeps the map in LDS
 
 __device__ __forceinline__ uint32_t bcnt_acc(uint32_t x, uint32_t acc) {
   // popcount + add in one VALU op (the compiler otherwise splits the sum into
@@ -2068,8 +2069,7 @@ FA_API int fa_hip_count_slab_rec_cls(const int64_t* roff, const int32_t* ranks, 
   const bool acc16 = (cls & 4) && !wword;   // two u16 counters per accumulator word
   const int64_t n_acc = acc16 ? (C + 1) / 2 : C;
   const bool contig = !bm && !src;
-  const size_t map_b = (contig && F1 <= kMapLdsMax) ? (size_t)(((int64_t)F1 * 2 + 15) & ~(int64_t)15) : 0;
-  const size_t lds = (size_t)n_used * (sw + 2) * 8 + (size_t)((n_acc + 3) & ~(int64_t)3) * 4 + map_b;
+  const size_t lds = (size_t)slab_kernel_lds(n_used, sw, slab_acc_words(n_acc), contig ? slab_map_lds(F1) : 0);
   if (lds > 160 * 1024 - 256) return 3;             // static build_words scratch
   if (g_slab_max_wg > 0) n_wg = std::min(n_wg, g_slab_max_wg);
   using KernT = void (*)(const int64_t*, const int32_t*, const int32_t*, int64_t, const int32_t*, int, int,

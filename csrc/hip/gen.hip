@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "fa_hip.h"
+#include "../host/fa_slab.h"
 
 namespace fa {
 
@@ -325,24 +326,7 @@ FA_API int fa_hip_ag_gen(const int32_t* P, int64_t n, int m, int F1, void* ws, i
 //   workspace / int32 of host buffer to retry with.
 //   host, per accepted level l: cnt [n_l] | ext [C_l] | rows [C_l][m_l + 1]
 //   (n_{l+1} = C_l, m_{l+1} = m_l + 1).
-// Bundle accumulator limit (fastapriori_amd ops.primitives.slab_capacity / slab_total_limit):
-// slab capacity for n_used items and C candidates, and the largest total t with
-// t <= capacity(t).
-static int64_t ag_slab_cap(int64_t n_used, int64_t C, double lds) {
-  for (int sw : {16, 32, 8, 4}) {      // plan.cpp slab_width order
-    const int64_t cap = (int64_t)((lds - (double)n_used * (sw + 2) * 8) / 4);
-    if (cap >= std::min<int64_t>(C, 8192) || (sw == 4 && cap >= 1024)) return cap;
-  }
-  return 0;
-}
-static int64_t ag_total_limit(int64_t n_used, double lds) {
-  int64_t lo = 0, hi = (int64_t)1 << 31;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) / 2;
-    if (mid <= ag_slab_cap(n_used, mid, lds)) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
+// Bundle accumulator limit: fa_slab.h slab_cap / slab_total_limit.
 
 // Per-level workspace init of the chain: hash table <- -1, Ext bitsets <- 0, off[0] <- 0.
 __global__ __launch_bounds__(256) void k_ag_init(int32_t* __restrict__ table, int64_t cap,
@@ -430,8 +414,8 @@ FA_API int fa_hip_ag_chain(const int32_t* P0, int64_t n0, int m0, int F1, void* 
       // level k's used items arrived with this sync: the bundle limit
       int64_t n_used = 0;
       for (int q = 0; q < MW; ++q) n_used += __builtin_popcount((uint32_t)host[q]);
-      tmax = ag_total_limit(n_used, lds);
-      if (total > ag_slab_cap(n_used, total, lds)) break;   // level k alone needs several passes
+      tmax = fa::slab_total_limit(n_used, lds, 4.0);
+      if (total > fa::slab_cap(n_used, total, lds, 4.0)) break;   // level k alone needs several passes
     }
     if (C == 0) break;
     if (!(first_free && l == 0) && ((double)C > growth * (double)last || total + C > tmax)) break;
@@ -468,46 +452,9 @@ FA_API int fa_hip_ag_chain(const int32_t* P0, int64_t n0, int m0, int F1, void* 
 }
 
 // ---------------------------------------------------------------------------
-// Device helpers of the speculative chains below: the slab accumulator limit
-// (ops.primitives.slab_capacity) and one row's pruned extension bits.
-// (A single cooperative kernel for the whole chain, every level's phases split by
-// grid barriers, measured slower than the kernel boundaries: removed.)
-// ---------------------------------------------------------------------------
-namespace fa {
-
-// accb: LDS bytes per accumulator (4, or 2 for count.hip's packed u16 counters)
-// capmax (fa_hip_set_cap_max): a bundle may take a narrower slab when that is what holds
-// all of its candidates (the first width whose capacity is >= C, else the largest
-// capacity); 0: the first width holding min(C, 8192), as plan.cpp slab_width
-__device__ int64_t d_slab_cap(int64_t n_used, int64_t C, double lds, double accb, int capmax = 0) {
-  const int sws[4] = {16, 32, 8, 4};   // plan.cpp slab_width order
-  int64_t best = 0;
-  for (int q = 0; q < 4; ++q) {
-    const int sw = sws[q];
-    const int64_t cap = (int64_t)((lds - (double)n_used * (sw + 2) * 8) / accb);
-    if (capmax) {
-      if (cap >= C && (sw != 4 || cap >= 1024)) return cap;
-      if (cap > best) best = cap;
-      continue;
-    }
-    if (cap >= (C < 8192 ? C : 8192) || (sw == 4 && cap >= 1024)) return cap;
-  }
-  return capmax ? best : 0;
-}
-
-__device__ int64_t d_total_limit(int64_t n_used, double lds, double accb) {
-  int64_t lo = 0, hi = (int64_t)1 << 31;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) / 2;
-    if (mid <= d_slab_cap(n_used, mid, lds, accb)) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-}  // namespace fa
-
-// ---------------------------------------------------------------------------
-// Device-sized speculative levels (first_free chains, after level 0).
+// Device-sized speculative levels (first_free chains, after level 0).  The slab
+// accumulator limit is fa_slab.h's slab_cap / slab_total_limit on the device (accb:
+// LDS bytes per accumulator, 4, or 2 for count.hip's packed u16 counters).
 //
 // fa_hip_ag_chain used to read every speculative level's candidate count back
 // before it could size and launch the next level: one host round trip per level
@@ -533,11 +480,11 @@ __global__ void k_agd_setup(long long* __restrict__ c, int64_t n1, int64_t total
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   int64_t n_used = 0;
   for (int q = 0; q < MW; ++q) n_used += __popc(mark[q]);
-  c[0] = total > d_slab_cap(n_used, total, lds, 4.0) ? 1 : 0;   // level k alone needs several passes
+  c[0] = total > slab_cap(n_used, total, lds, 4.0) ? 1 : 0;   // level k alone needs several passes
   c[1] = 1;
   c[2] = total;
   c[3] = last;
-  c[4] = d_total_limit(n_used, lds, 4.0);
+  c[4] = slab_total_limit(n_used, lds, 4.0);
   c[9] = n1;
 }
 
@@ -951,8 +898,7 @@ __global__ __launch_bounds__(256) void k_dl_mark(const int32_t* __restrict__ row
 }
 
 // n_used, and whether level 0 alone exceeds one accumulator pass
-__global__ __launch_bounds__(64) void k_dl_post0(long long* __restrict__ c, double lds, double accb, int w32,
-                                                  int capmax) {
+__global__ __launch_bounds__(64) void k_dl_post0(long long* __restrict__ c, double lds, double accb, int w32) {
   if (blockIdx.x != 0) return;
   const uint32_t* mk = reinterpret_cast<const uint32_t*>(c + kDlBits);
   uint32_t part = 0;
@@ -960,21 +906,21 @@ __global__ __launch_bounds__(64) void k_dl_post0(long long* __restrict__ c, doub
   const int64_t n_used = (int64_t)wave_sum_u32(part);
   if (threadIdx.x != 0) return;
   c[6] = n_used;
-  if (c[1] == 1 && c[40] > d_slab_cap(n_used, c[40], lds, accb, capmax)) { c[5] = 1; c[0] = 1; }
+  if (c[1] == 1 && c[40] > slab_cap(n_used, c[40], lds, accb)) { c[5] = 1; c[0] = 1; }
 }
 
 // acceptance of speculative level l >= 1 (same rule as k_agd_scan_decide, with the
 // exact one-pass test total + C <= slab capacity(n_used, total + C))
 __global__ __launch_bounds__(1024) void k_dl_decide(const int32_t* __restrict__ cnt, int64_t* __restrict__ off,
                                                      long long* __restrict__ c, int l, double growth, int64_t c_bound,
-                                                     double lds, double accb, int capmax) {
+                                                     double lds, double accb) {
   if (c[0]) return;
   int64_t g = 0;
   const int64_t C = agd_block_scan(cnt, off, c[8 + l], &g);
   if (threadIdx.x != 0) return;
   const int64_t total = c[2], last = c[3];
   if (C == 0 || (double)C > growth * (double)last || C > c_bound ||
-      total + C > d_slab_cap(c[6], total + C, lds, accb, capmax)) {
+      total + C > slab_cap(c[6], total + C, lds, accb)) {
     c[0] = 1;
     // no candidates even from the previous level's candidates (a superset of its
     // frequent rows): the mining ends with this bundle (the host skips the next one)
@@ -1042,11 +988,6 @@ __global__ __launch_bounds__(256) void k_dl_rows(const int32_t* __restrict__ P, 
 
 }  // namespace fa
 
-// Slab capacity rule of the device bundles (d_slab_cap capmax), set by
-// fastapriori_amd.ops.primitives before a bundle is generated (TUNING.slab_cap_max)
-static int g_cap_max = 0;
-FA_API void fa_hip_set_cap_max(int on) { g_cap_max = on; }
-
 // Level 0 of a device bundle: candidates of F_{k-1} = P0 [n][m0] (device; n from
 // n_src[0] when given, else n_const; n_bound >= n sizes the buffers), generated
 // into the front of ws; with sync, ONE synchronisation copies ctl to ctl_host
@@ -1110,7 +1051,7 @@ FA_API int fa_hip_dl_level0(const int32_t* P0, const long long* n_src, int64_t n
   const int w32 = (F1 + 31) / 32;
   hipLaunchKernelGGL(k_dl_mark, dim3((unsigned)std::min<int64_t>((c_bound * (m0 + 1) + 255) / 256, 1024)), dim3(256),
                      0, st, rows, m0 + 1, ctl, w32);
-  hipLaunchKernelGGL(k_dl_post0, dim3(1), dim3(64), 0, st, ctl, lds, accb, w32, g_cap_max);
+  hipLaunchKernelGGL(k_dl_post0, dim3(1), dim3(64), 0, st, ctl, lds, accb, w32);
   if (sync) {
     (void)hipMemcpyAsync(ctl_host, ctl, sizeof(long long) * kDlCtl, hipMemcpyDeviceToHost, st);
     if (hipStreamSynchronize(st) != hipSuccess) return 7;
@@ -1173,20 +1114,6 @@ FA_API int fa_hip_count_slab_rec_cls(const int64_t* roff, const int32_t* ranks, 
                                      int n_wg, const uint64_t* bm, int64_t Wp, hipStream_t st,
                                      const int32_t* bm_rows, const int32_t* g_dev, int cls);
 
-// P[Binom(L, p) >= k] (the regularised incomplete beta of FastApriori._trim_worth_it)
-static double binom_tail(int L, double p, int k) {
-  if (L < k) return 0.0;
-  if (p <= 0.0) return k <= 0 ? 1.0 : 0.0;
-  if (p >= 1.0) return 1.0;
-  double pmf = std::pow(1.0 - p, (double)L), below = 0.0;
-  const double r = p / (1.0 - p);
-  for (int i = 0; i < k; ++i) {
-    below += pmf;
-    pmf *= (double)(L - i) / (double)(i + 1) * r;
-  }
-  return std::min(1.0, std::max(0.0, 1.0 - below));
-}
-
 static void dl_post(DlPost* P, const int64_t* desc, int L, long long* ctl, const long long* ch, int F1,
                     hipStream_t st) {
   P->done = 0;
@@ -1197,15 +1124,9 @@ static void dl_post(DlPost* P, const int64_t* desc, int L, long long* ctl, const
   const int64_t n_used = ch[6];
   P->C = C;
   if (C < 1 || C > P->rec_cap || C > P->out_cap || 8 * ((R + 255) / 256) > P->part_cap) return;
-  // slab width: plan.cpp slab_width order, one accumulator pass
-  int sw = 0;
+  // slab width (fa_slab.h), one accumulator pass
   int64_t cap = 0;
-  for (int w : {16, 32, 8, 4}) {
-    cap = (int64_t)((P->lds_budget - (double)n_used * (w + 2) * 8) / P->accb);
-    const bool fits = g_cap_max ? cap >= C && (w != 4 || cap >= 1024)
-                                : cap >= std::min<int64_t>(C, 8192) || (w == 4 && cap >= 1024);
-    if (fits) { sw = w; break; }
-  }
+  const int sw = slab_width(n_used, C, P->lds_budget, P->accb, &cap);
   if (sw == 0 || C > cap) return;
   if (fa_hip_dl_plan(desc, L, ctl, F1, P->item_map, P->rec, C, P->part, P->part_cap, P->gpre, P->gpre_cap, sw,
                      st) != 0)
@@ -1228,26 +1149,18 @@ static void dl_post(DlPost* P, const int64_t* desc, int L, long long* ctl, const
       if ((mk[r >> 6] >> (r & 63)) & 1ull) num += (double)P->c1[r];
     }
     if (den > 0.0) {
-      const double p = num / den;
       double est_rows = 0.0, est_nnz = 0.0;
-      for (int Lr = 0; Lr < 256; ++Lr) {
-        const double h = (double)P->len_hist[Lr];
-        if (h == 0.0) continue;
-        est_rows += h * binom_tail(Lr, p, (int)P->k);
-        est_nnz += h * Lr * p;
-      }
+      trim_estimate(P->len_hist, 256, num / den, (int)P->k, &est_rows, &est_nnz);
       const double T = (double)std::max<int64_t>(P->T, 1), nnz = (double)std::max<int64_t>(P->nnz, 1);
       P->trim = (est_rows < P->trim_rows_frac * T || est_nnz < P->trim_nnz_frac * nnz) ? 1 : 0;
     }
   }
   if (P->trim) return;                                      // the caller trims, then counts
   const int64_t W = (P->ncols + 63) / 64, nslabs = (W + sw - 1) / sw;
-  const int64_t map_b = F1 <= 8192 ? (((int64_t)F1 * 2 + 15) & ~(int64_t)15) : 0;
   const bool acc16 = P->accb == 2.0 && !P->wword;
   const int64_t nacc = acc16 ? (C + 1) / 2 : C;
-  const int64_t lds_k = n_used * (sw + 2) * 8 + ((nacc + 3) & ~(int64_t)3) * 4 + map_b;
-  const int64_t per_cu = std::min<int64_t>(std::max<int64_t>(1, (int64_t)P->lds_kernel / std::max<int64_t>(lds_k, 1)), 2);
-  P->n_wg = std::max<int64_t>(1, std::min<int64_t>(nslabs, 256 * per_cu));
+  P->n_wg = slab_workgroups(nslabs, (int64_t)P->lds_kernel,
+                            slab_kernel_lds(n_used, sw, slab_acc_words(nacc), slab_map_lds(F1)));
   if (fa_hip_count_slab_rec_cls(P->roff, P->ranks, P->src, P->ncols, P->item_map, F1, (int)n_used, P->gpre, P->rec,
                                 0, (int)C, P->wword, P->out, sw, (int)P->n_wg, nullptr, 0, st, nullptr,
                                 reinterpret_cast<const int32_t*>(ctl + 221), acc16 ? 4 : 0) != 0)
@@ -1330,8 +1243,8 @@ FA_API int fa_hip_dl_more(int F1, void* ws, int64_t ws_bytes, int64_t ws_used, l
 #define FA_DLR_CNT(N) FA_DLR(false, N)
 #define FA_DLR_EMIT(N) FA_DLR(true, N)
       FA_AG_NWL_SWITCH(nw, FA_DLR_CNT)
-      hipLaunchKernelGGL(k_dl_decide, dim3(1), dim3(1024), 0, st, lv[l].cnt, lv[l].off, ctl, l, growth, cb, lds, accb,
-                         g_cap_max);
+      hipLaunchKernelGGL(k_dl_decide, dim3(1), dim3(1024), 0, st, lv[l].cnt, lv[l].off, ctl, l, growth, cb, lds,
+                         accb);
       FA_AG_NWL_SWITCH(nw, FA_DLR_EMIT)
 #undef FA_DLR_EMIT
 #undef FA_DLR_CNT

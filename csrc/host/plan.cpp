@@ -13,8 +13,31 @@
 #include <vector>
 
 #include "fa_common.h"
+#include "fa_slab.h"
 
 using namespace fa;
+
+// ---------------------------------------------------------------------------
+// The slab rule of fa_slab.h for fastapriori_amd.ops.primitives (ctypes): Python
+// holds no copy of it.
+// ---------------------------------------------------------------------------
+FA_API int fa_slab_width(int64_t n_used, int64_t C, double lds, double accb, int64_t* cap) {
+  return slab_width(n_used, C, lds, accb, cap);
+}
+FA_API int64_t fa_slab_total_limit(int64_t n_used, double lds, double accb) {
+  return slab_total_limit(n_used, lds, accb);
+}
+FA_API int64_t fa_slab_map_lds(int64_t F1) { return slab_map_lds(F1); }
+// n_acc accumulator words (round_acc: rounded as the kernel allocates them), map_bytes
+// of rank map, budget: LDS bytes of a CU's share
+FA_API int64_t fa_slab_workgroups(int64_t nslabs, int64_t n_used, int sw, int64_t n_acc, int round_acc,
+                                  int64_t map_bytes, int64_t budget) {
+  return slab_workgroups(nslabs, budget,
+                         slab_kernel_lds(n_used, sw, round_acc ? slab_acc_words(n_acc) : n_acc, map_bytes));
+}
+FA_API void fa_trim_estimate(const int64_t* len_hist, int64_t n_bins, double p, int k, double* rows, double* nnz) {
+  trim_estimate(len_hist, n_bins, p, k, rows, nnz);
+}
 
 // ---------------------------------------------------------------------------
 // One-call level planner: everything the level kernels need, computed in C++
@@ -31,24 +54,9 @@ using namespace fa;
 //     23 class layout used by some pass (record flags set: k_count_slab_rec<.., kCls>)
 //   passes (int64[3 * maxpass]): (piece begin, piece end, ext base)
 // Returns 0, 3 (buffer too small), 4 (no slab width fits: use the bitmap kernel).
+// The slab width and capacity come from fa_slab.h (slab_width), with the LDS copy of
+// the rank -> slab-row map subtracted from the budget here.
 // ---------------------------------------------------------------------------
-// Width order 16, 32, 8, 4: measured per slab column on MI355X (T40I10D100M levels
-// 7-10, k_count_slab_rec), 64-B rows read ~0.43x and 256-B rows ~0.55x as many
-// columns per second as 128-B rows (the 256-B form holds 16 uint4 of prefix AND
-// per thread: fewer waves, longer row scans per LDS bank).
-static int slab_width(int64_t n_used, int64_t C, double lds, int64_t* cap_out, double accb = 4,
-                      double map_lds = 0) {
-  for (int sw : {16, 32, 8, 4}) {
-    // + the LDS copy of the rank -> slab-row map (u16 per frequent item, k_count_slab_rec)
-    const int64_t cap = (int64_t)((lds - (double)n_used * (sw + 2) * 8 - map_lds) / accb);
-    if (cap >= std::min<int64_t>(C, 8192) || (sw == 4 && cap >= 1024)) { *cap_out = cap; return sw; }
-  }
-  return 0;
-}
-
-// LDS bytes of k_count_slab_rec's copy of the rank -> slab-row map (u16 per
-// frequent item; 0 = the map stays in global memory).  count.hip mirrors this.
-static inline int64_t fa_slab_map_lds(int64_t F1) { return F1 <= 8192 ? ((F1 * 2 + 15) & ~(int64_t)15) : 0; }
 
 // ---------------------------------------------------------------------------
 // Class layout of a slab pass (k_count_slab_rec<.., kCls>).  Pieces whose prefixes
@@ -212,7 +220,7 @@ FA_API int fa_level_plan(const int32_t* Pf, const int64_t* poff, int64_t G, cons
 
   // ---- slab kernel: pieces of <= 8 extensions, passes of <= cap, size-sorted per pass
   int64_t cap = 0;
-  const int sw = slab_width(n_used, C, lds, &cap, accb, (double)fa_slab_map_lds(F1));
+  const int sw = slab_width(n_used, C, lds - (double)slab_map_lds(F1), accb, &cap);
   if (sw == 0) return 4;
   std::vector<SlabPiece> pcs;
   pcs.reserve((size_t)pieces8);

@@ -50,6 +50,12 @@ void fa_cpu_pair_gram(const uint64_t* bm, int32_t F1, int64_t Wp, int64_t W, con
 void fa_cpu_pair_horizontal(const int64_t* roff, const int32_t* ranks, int64_t T, const int32_t* wrow, int32_t F1,
                             int64_t* out, int nthreads);
 void fa_cpu_row_hash(const int64_t* roff, const int32_t* ranks, int64_t T, int64_t* h1, int64_t* h2, int nthreads);
+int fa_slab_width(int64_t n_used, int64_t C, double lds, double accb, int64_t* cap);
+int64_t fa_slab_total_limit(int64_t n_used, double lds, double accb);
+int64_t fa_slab_map_lds(int64_t F1);
+int64_t fa_slab_workgroups(int64_t nslabs, int64_t n_used, int sw, int64_t n_acc, int round_acc, int64_t map_bytes,
+                           int64_t budget);
+void fa_trim_estimate(const int64_t* len_hist, int64_t n_bins, double p, int k, double* rows, double* nnz);
 }
 
 static int g_fail = 0;
@@ -308,8 +314,42 @@ static void test_kernels_and_rules(int nt) {
   }
 }
 
+// The slab rule (fa_slab.h) at hand-computed points; tests/test_slab_rule.py sweeps it.
+static void test_slab_rule() {
+  const double lds = 163328;
+  struct { int64_t n, C; double accb; int sw; int64_t cap; } cases[] = {
+      {300, 1000, 4, 16, 30032},    // 163328 - 300 * 144 = 120128
+      {974, 40000, 4, 8, 21352},    // width 16 holds 5768 < 8192; width 8: 85408 / 4
+      {974, 40000, 2, 16, 11536},   // u16 accumulators: width 16 holds 23072 / 2
+      {2000, 8192, 4, 4, 16832},    // width 8 holds 832; width 4: 67328 / 4
+      {3000, 40000, 4, 4, 4832},    // width 4 below 8192 but >= 1024
+      {3000, 1023, 4, 4, 4832},
+      {5000, 1, 4, 0, 0},           // 5000 * 48 > lds
+      {0, 1 << 20, 4, 16, 40832},
+  };
+  for (const auto& c : cases) {
+    int64_t cap = -1;
+    CHECK(fa_slab_width(c.n, c.C, lds, c.accb, &cap) == c.sw);
+    CHECK(cap == c.cap);
+  }
+  CHECK(fa_slab_total_limit(974, lds, 4) == 21352);
+  CHECK(fa_slab_total_limit(5000, lds, 4) == 0);
+  CHECK(fa_slab_map_lds(1) == 16 && fa_slab_map_lds(8) == 16 && fa_slab_map_lds(8192) == 16384 &&
+        fa_slab_map_lds(8193) == 0);
+  CHECK(fa_slab_workgroups(1000, 300, 16, 1000, 1, 0, 163328) == 512);    // 47200 B: two per CU
+  CHECK(fa_slab_workgroups(1000, 974, 8, 21352, 1, 1952, 163328) == 256);  // 165280 B: one per CU
+  CHECK(fa_slab_workgroups(3, 300, 16, 1000, 0, 0, 163328) == 3);
+  const int64_t one[1] = {5}, five[5] = {0, 0, 0, 0, 8};
+  double rows = -1, nnz = -1;
+  fa_trim_estimate(one, 1, 0.5, 3, &rows, &nnz);
+  CHECK(rows == 0.0 && nnz == 0.0);
+  fa_trim_estimate(five, 5, 0.5, 3, &rows, &nnz);     // P[Binom(4, 1/2) >= 3] = 5/16
+  CHECK(rows > 2.5 - 1e-12 && rows < 2.5 + 1e-12 && nnz == 16.0);
+}
+
 int main(int argc, char** argv) {
   const int nt = argc > 1 ? std::atoi(argv[1]) : 8;
+  test_slab_rule();
   test_parser(nt);
   test_generators(nt);
   test_apriori_gen(nt);

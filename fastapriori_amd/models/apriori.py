@@ -541,7 +541,7 @@ class FastApriori:
         bits = np.unpackbits(c[Pm.DL_BITS:Pm.DL_BITS + nwd].view(np.uint8), bitorder="little")[:F1]
         used = np.flatnonzero(bits)
         n_used = int(used.size)
-        wide = Pm.dl_slab_width(n_used, min(C0, 8192), lds, self._dl_mp_accb)[0] == 0
+        wide = Pm.slab_width(n_used, C0, lds, self._dl_mp_accb)[0] == 0
         with self._timer.phase(f"trim{k}"), roctx_range("trim"):
             self._trim(db, used, k, C0)
         v = self._count_view(db)
@@ -614,9 +614,8 @@ class FastApriori:
         """Rows expected to keep >= k of the items `used` (and, with_nnz, the item
         occurrences they keep): item occurrences survive with probability p = (supports
         of `used`) / (supports of the items still in the rows), a row of length L keeps
-        >= k with P[Binom(L, p) >= k] = I_p(k, L - k + 1) (regularised incomplete beta).
-        None without a length histogram or items."""
-        from scipy.special import betainc
+        >= k with P[Binom(L, p) >= k] (csrc/host/fa_slab.h trim_estimate, the estimate the
+        device bundles' post step takes).  None without a length histogram or items."""
         hist = db.get("len_hist")
         if hist is None:
             return None
@@ -625,13 +624,8 @@ class FastApriori:
         if denom <= 0:
             return None
         p = min(float(c1[used].sum()) / denom, 1.0)
-        L = np.arange(hist.size)
-        sf = np.zeros(hist.size)
-        ok = L >= k
-        if p > 0:
-            sf[ok] = betainc(k, L[ok] - k + 1, p)
-        rows = float((hist * sf).sum())
-        return (rows, float((hist * L * p).sum())) if with_nnz else rows
+        rows, nnz = ops.primitives.trim_estimate(hist, p, k)
+        return (rows, nnz) if with_nnz else rows
 
     def _dl_bitmap_count(self, S, db, used: np.ndarray) -> torch.Tensor:
         """Counts (int32 [C], bundle order) of the device bundle's single level from the
@@ -1274,6 +1268,12 @@ class FastApriori:
         wword = torch.repeat_interleave(cls_w.to(torch.int32), padded // 64)
         db.update(src=src, ncols=ncols, wword=wword, wcls=(wcls[0], wcls[1]))
 
+    @staticmethod
+    def _slab_cap(n_used: int, C: int) -> int:
+        """The host loop's accumulator capacity per pass: the whole TUNING.slab_lds_bytes,
+        rank map not subtracted (csrc/host/fa_slab.h lists the callers' budgets)."""
+        return ops.primitives.slab_width(n_used, C, TUNING.slab_lds_bytes)[1]
+
     def _trim_worth_it(self, db, used: np.ndarray, k: int, C: int = 0) -> bool:
         """Binomial estimate of the rows that would survive trimming.
 
@@ -1292,7 +1292,7 @@ class FastApriori:
             return False
         est_rows, est_nnz = got
         rows_ok = est_rows < TUNING.trim_rows_frac * max(db["T"], 1)
-        if C and db["ranks"].is_cuda and C > ops.primitives.slab_capacity(int(used.size), C):
+        if C and db["ranks"].is_cuda and C > self._slab_cap(int(used.size), C):
             return rows_ok
         return rows_ok or est_nnz < TUNING.trim_nnz_frac * max(int(db["ranks"].numel()), 1)
 
@@ -1317,7 +1317,7 @@ class FastApriori:
         # a level counted window by window streams its slabs from the used items' bitmap,
         # whose cost follows the rows only: fewer items alone do not pay for a new layout
         # (and the bitmap rebuild it forces)
-        multi = bool(C) and db["ranks"].is_cuda and C > ops.primitives.slab_capacity(int(used.size), C)
+        multi = bool(C) and db["ranks"].is_cuda and C > self._slab_cap(int(used.size), C)
         if K > 0.9 * db["T"] and (multi or nranks.numel() > 0.9 * db["ranks"].numel()):
             return   # not worth re-laying out
         db.update(roff=nroff, ranks=nranks, T=K, bm=None, W=0, bcnt=None, bm_items=None, bm_map=None)
@@ -1558,7 +1558,7 @@ class FastApriori:
         items[self._bundle_rows[0].ravel()] = True
         total = C
         n_used = int(items.sum())
-        if total > ops.primitives.slab_capacity(n_used, total):
+        if total > self._slab_cap(n_used, total):
             return bundle
         cand = self._bundle_rows[0]
         last = C
@@ -1568,7 +1568,7 @@ class FastApriori:
                 and self._F1 <= ops.primitives.AG_DEVICE_MAX_F1):
             # all speculative levels in one native call (one 8-byte readback per level)
             max_lv = (self.cfg.max_level - k) if self.cfg.max_level else 64
-            tmax = ops.primitives.slab_total_limit(n_used)
+            tmax = ops.primitives.slab_total_limit(n_used, TUNING.slab_lds_bytes)
             for pi, eo, ex, nxt in ops.primitives.apriori_gen_chain(cand, self._F1, dev, max_lv,
                                                                     TUNING.bundle_growth, total, tmax):
                 kk += 1
@@ -1582,7 +1582,7 @@ class FastApriori:
             if C2 == 0 or C2 > TUNING.bundle_growth * last:
                 break
             # later levels only use items of level k's candidates: n_used is fixed
-            if total + C2 > ops.primitives.slab_capacity(n_used, total + C2):
+            if total + C2 > self._slab_cap(n_used, total + C2):
                 break
             kk += 1
             bundle.append((kk, cand, pi, eo, ex))

@@ -42,6 +42,12 @@ _HOST_SIGS = {
     "fa_cands_export": (None, [vp, vp, vp, vp]),
     "fa_cands_free": (None, [vp]),
     "fa_level_plan": (C.c_int, [vp, vp, i64, vp, vp, i32, vp, vp, i64, vp, i64, vp]),
+    # the slab kernel's LDS rule and the trimming estimate (csrc/host/fa_slab.h)
+    "fa_slab_width": (C.c_int, [i64, i64, dbl, dbl, I64P]),
+    "fa_slab_total_limit": (i64, [i64, dbl, dbl]),
+    "fa_slab_map_lds": (i64, [i64]),
+    "fa_slab_workgroups": (i64, [i64, i64, C.c_int, i64, C.c_int, i64, i64]),
+    "fa_trim_estimate": (None, [vp, i64, dbl, C.c_int, C.POINTER(dbl), C.POINTER(dbl)]),
     "fa_f1_rank_numeric": (i64, [vp, i64, i64, vp, vp, vp]),
     "fa_rules_build": (vp, [vp, vp, vp, C.c_int, vp, C.c_int, vp]),
     "fa_rules_nante": (i64, [vp]),
@@ -98,7 +104,6 @@ _HIP_SIGS = {
     "fa_hip_dl_more": (C.c_int, [C.c_int, vp, i64, i64, vp, vp, dbl, C.c_int, dbl, dbl, i64, vp, vp, vp, vp]),
     "fa_hip_dl_plan": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, i64, vp, i64, vp, i64, C.c_int, vp]),
     "fa_hip_set_lane_deal": (None, [C.c_int]),
-    "fa_hip_set_cap_max": (None, [C.c_int]),
     "fa_hip_set_piece_part": (C.c_int, [C.c_int, C.c_int]),
     "fa_hip_dl_gpre_need": (i64, [vp, C.c_int]),
     "fa_hip_dl_plan_window": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, i64, vp, i64, vp, i64, i64, i64, C.c_int,

@@ -64,7 +64,9 @@ def hip_sources() -> list[str]:
 def _deps(kind: str) -> list[str]:
     if kind == "host":
         return host_sources() + sorted(glob.glob(os.path.join(CSRC, "host", "*.h")))
-    return hip_sources() + sorted(glob.glob(os.path.join(CSRC, "hip", "*.h")))
+    # + the slab rule the kernels share with the host planner (included by relative path)
+    return hip_sources() + sorted(glob.glob(os.path.join(CSRC, "hip", "*.h"))) + [
+        os.path.join(CSRC, "host", "fa_slab.h")]
 
 
 def source_id(kind: str, flags: list[str] | None = None) -> str:

@@ -834,14 +834,40 @@ def trim_rows(roff, ranks, alive: torch.Tensor, min_len: int, wrow=None):
     return kept, nroff, nranks[:nnz], nw, hist
 
 
-def slab_capacity(n_used: int, C: int) -> int:
-    """Accumulator capacity (candidates per pass) of the slab kernel for n_used items
-    (csrc/host/plan.cpp slab_width); 0 when no width fits."""
-    for sw in (16, 32, 8, 4):     # plan.cpp slab_width order
-        cap = int((TUNING.slab_lds_bytes - n_used * (sw + 2) * 8) // 4)
-        if cap >= min(C, 8192) or (sw == 4 and cap >= 1024):
-            return cap
-    return 0
+def slab_width(n_used: int, C: int, lds: int, accb: int = 4) -> tuple[int, int]:
+    """The slab kernel's (SW, accumulator capacity per pass) for n_used items and C
+    candidates in lds bytes of slab + accumulators (accb: LDS bytes per accumulator);
+    (0, 0) when no width fits.  The rule itself is csrc/host/fa_slab.h, which also says
+    which callers pass a budget with the rank map subtracted (dl_lds_budget)."""
+    cap = ctypes.c_int64(0)
+    sw = _native.host().fa_slab_width(int(n_used), int(C), float(lds), float(accb), ctypes.byref(cap))
+    return int(sw), int(cap.value)
+
+
+def slab_total_limit(n_used: int, lds: int, accb: int = 4) -> int:
+    """Largest bundle total t with t <= slab_width(n_used, t, lds, accb)[1]."""
+    return int(_native.host().fa_slab_total_limit(int(n_used), float(lds), float(accb)))
+
+
+def slab_map_lds(F1: int) -> int:
+    """LDS bytes of k_count_slab_rec's u16 rank -> slab-row map (0: it stays in global memory)."""
+    return int(_native.host().fa_slab_map_lds(int(F1)))
+
+
+def trim_estimate(len_hist: np.ndarray, p: float, k: int) -> tuple[float, float]:
+    """(rows expected to keep >= k items, item occurrences kept) when an occurrence
+    survives with probability p and len_hist[L] rows have length L (fa_slab.h trim_estimate)."""
+    hist = np.ascontiguousarray(len_hist, dtype=np.int64)
+    rows, nnz = ctypes.c_double(0.0), ctypes.c_double(0.0)
+    _native.host().fa_trim_estimate(hist.ctypes.data, hist.size, float(p), int(k), ctypes.byref(rows),
+                                    ctypes.byref(nnz))
+    return rows.value, nnz.value
+
+
+def _slab_workgroups(nslabs: int, n_used: int, sw: int, n_acc: int, round_acc: bool, map_bytes: int) -> int:
+    """Workgroups of a slab count (fa_slab.h slab_workgroups) within TUNING.slab_lds_bytes."""
+    return int(_native.host().fa_slab_workgroups(int(nslabs), int(n_used), int(sw), int(n_acc), int(round_acc),
+                                                 int(map_bytes), int(TUNING.slab_lds_bytes)))
 
 
 # TUNING.slab_cls: class layout of slab passes (plan.cpp cls_layout, k_count_slab_rec<..,
@@ -940,11 +966,6 @@ LAST_LEVEL_PLAN: dict = {}   # shape of the last count_level call (diagnostics)
 CLS_LEVELS = [0]             # count_level calls that ran the class layout (diagnostics, tests)
 
 
-def _slab_map_lds(F1: int) -> int:
-    """LDS bytes of k_count_slab_rec's u16 rank -> slab-row map (plan.cpp fa_slab_map_lds)."""
-    return ((F1 * 2 + 15) & ~15) if F1 <= 8192 else 0
-
-
 def _flat_prefix(prefix: np.ndarray, poff: np.ndarray | None):
     if poff is None:
         P = np.ascontiguousarray(prefix, dtype=np.int32)
@@ -1029,11 +1050,11 @@ def count_level(roff, ranks, src, ncols: int, F1: int, prefix: np.ndarray, ext_o
     bounds = passes[:, 2].tolist() + [C]
     nslabs = (W + sw - 1) // sw
     dense = wword is None and TUNING.dense_min_rows > 0 and sup_frac * sw * 64 >= TUNING.dense_min_rows
+    map_b = slab_map_lds(F1)
     for q, (a, b, e0) in enumerate(passes.tolist()):
         Cq = bounds[q + 1] - e0
         # piece records (k_count_slab_rec): 48 B per piece, loaded one piece ahead
-        lds = n_used * (sw + 2) * 8 + Cq * 4 + _slab_map_lds(F1)
-        n_wg = int(max(1, min(nslabs, 256 * min(max(1, TUNING.slab_lds_bytes // lds), 2))))
+        n_wg = _slab_workgroups(nslabs, n_used, sw, Cq, False, map_b)
         _hip_call("fa_hip_count_slab_rec_cls", _p(roff), _p(ranks), _p(src), ncols, base + 4 * o_im, F1,
                   n_used, base + 4 * o_gpre, base + 4 * (o_rec + 12 * a), b - a, Cq, _p(wword),
                   out.data_ptr() + 4 * e0, sw, n_wg, _p(bm), bitmap_ld(bm), st,
@@ -1166,18 +1187,6 @@ def apriori_gen_chain(rows: np.ndarray, F1: int, dev, max_levels: int, growth: f
         o += n + C + C * (m + 1)
         n, m = C, m + 1
     return out
-
-
-def slab_total_limit(n_used: int) -> int:
-    """Largest bundle total t with t <= slab_capacity(n_used, t) (monotone in t)."""
-    lo, hi = 0, 1 << 31
-    while lo < hi:
-        mid = (lo + hi + 1) // 2
-        if mid <= slab_capacity(n_used, mid):
-            lo = mid
-        else:
-            hi = mid - 1
-    return lo
 
 
 RECOMMEND_INDEX_MIN_RULES = 2048
@@ -1604,8 +1613,8 @@ def device_level_state(dev) -> DeviceLevelState:
 
 def dl_lds_budget(F1: int) -> int:
     """LDS bytes left to slab + accumulators in k_count_slab_rec (the rank map's copy
-    subtracted, as plan.cpp slab_width does)."""
-    return TUNING.slab_lds_bytes - _slab_map_lds(F1)
+    subtracted, as plan.cpp does)."""
+    return TUNING.slab_lds_bytes - slab_map_lds(F1)
 
 
 # TUNING.dl_acc16: window-by-window device levels count into two u16 counters per
@@ -1613,20 +1622,6 @@ def dl_lds_budget(F1: int) -> int:
 # the passes.  One-pass bundles keep u32 accumulators: with u16 ones the larger capacity
 # made the generator pick 16-word slabs for level 3 alone and cut the later bundles
 # differently, T10I4D100M 43.2 vs 42.3 ms (docs/PERF_HISTORY.md; that arm was removed)
-
-
-def dl_slab_width(n_used: int, C: int, lds: int, accb: int = 4, cap_max: bool = False) -> tuple[int, int]:
-    """plan.cpp slab_width: (SW, accumulator capacity) for n_used items and C candidates
-    (accb: LDS bytes per accumulator).  cap_max (TUNING.slab_cap_max, gen.hip
-    d_slab_cap): the first width whose capacity holds all C candidates."""
-    for sw in (16, 32, 8, 4):
-        cap = int((lds - n_used * (sw + 2) * 8) // accb)
-        if cap_max:
-            if cap >= C and (sw != 4 or cap >= 1024):
-                return sw, cap
-        elif cap >= min(C, 8192) or (sw == 4 and cap >= 1024):
-            return sw, cap
-    return 0, 0
 
 
 def dl_bundle_gen(S: DeviceLevelState, P0: int, n_src: int | None, n_const: int, n_bound: int, m0: int, F1: int,
@@ -1638,7 +1633,6 @@ def dl_bundle_gen(S: DeviceLevelState, P0: int, n_src: int | None, n_const: int,
     describes the accepted levels (L = ctl[1])."""
     lib = _native.hip()
     info = np.zeros(2, dtype=np.int64)
-    lib.fa_hip_set_cap_max(int(TUNING.slab_cap_max))
     for _ in range(6):
         S.desc[:] = 0
         rc = lib.fa_hip_dl_level0(P0, n_src, n_const, n_bound, m0, F1, _p(S.ws), S.ws.numel(), _p(S.ctl),
@@ -1686,7 +1680,7 @@ def dl_plan(S: DeviceLevelState, L: int, F1: int, n_used: int, C: int, lds: int,
     candidates only, not on the row layout, so the host's trimming decision runs
     while it executes.  Returns the plan for dl_count."""
     st = torch.cuda.current_stream(dev).cuda_stream
-    sw, cap = dl_slab_width(n_used, C, lds, accb, TUNING.slab_cap_max)
+    sw, cap = slab_width(n_used, C, lds, accb)
     if sw == 0 or C > cap:
         raise RuntimeError(f"device bundle of {C} candidates over {n_used} items does not fit one pass")
     item_map = torch.empty(max(F1, 1), dtype=_I32, device=dev)
@@ -1725,7 +1719,7 @@ def dl_count_multipass(S: DeviceLevelState, F1: int, n_used: int, C: int, lds: i
     window's k-candidates), counted instead of the level's bitmap."""
     acc16 = TUNING.dl_acc16 and wword is None
     accb = 2 if acc16 else 4
-    sw, cap = dl_slab_width(n_used, min(C, 8192), lds, accb)
+    sw, cap = slab_width(n_used, C, lds, accb)
     if sw == 0:
         return None
     st = _stream(ranks)
@@ -1772,8 +1766,7 @@ def dl_count_multipass(S: DeviceLevelState, F1: int, n_used: int, C: int, lds: i
                                                      _p(rec), cap, _p(part), part.numel(), _p(gpre), gpre.numel(),
                                                      w0, w1, wsw, st), "fa_hip_dl_plan_window_bits")
         nacc = (w1 - w0 + 1) // 2 if acc16 else w1 - w0
-        lds_k = nu * (wsw + 2) * 8 + ((nacc + 3) & ~3) * 4
-        n_wg = int(max(1, min(nslabs, 256 * min(max(1, TUNING.slab_lds_bytes // lds_k), 2))))
+        n_wg = _slab_workgroups(nslabs, nu, wsw, nacc, True, 0)
         _hip_call("fa_hip_count_slab_rec_cls", _p(roff), _p(ranks), _p(src), ncols_w, _p(item_map), F1, nu,
                   _p(gpre), _p(rec), 0, w1 - w0, _p(wword), out.data_ptr() + 4 * w0, wsw, n_wg, _p(bm_w),
                   bitmap_ld(bm_w), st, _p(rows_w), _p(S.ctl) + 8 * 221, (2 if dense else 0) | (4 if acc16 else 0))
@@ -1841,7 +1834,7 @@ def dl_window_plan(S: DeviceLevelState, F1: int, C: int, lds: int, accb: int, st
     own used items: the used-item bitset of every chunk of candidates
     (levels.hip fa_hip_dl_chunk_bits, one small readback), then, greedily, the longest run
     of chunks whose item union leaves accumulators for all of its candidates at the
-    widest slab holding min(candidates, 8192) (dl_slab_width).  Returns [(w0, w1, sw,
+    slab width of the rule (slab_width).  Returns [(w0, w1, sw,
     uint64 bitset [nwd])], or None when F1 is too wide for the bitsets."""
     nwd = (F1 + 63) // 64
     if nwd > 512 or C < 1:
@@ -1861,7 +1854,7 @@ def dl_window_plan(S: DeviceLevelState, F1: int, C: int, lds: int, accb: int, st
             a2 = acc | bits[k]
             n = int(pop8[a2.view(np.uint8)].sum())
             cand = min((k + 1) * chunk, C) - j * chunk
-            sw, cap = dl_slab_width(n, min(cand, 8192), lds, accb)
+            sw, cap = slab_width(n, cand, lds, accb)
             if sw == 0 or cap < cand:
                 break
             acc, best = a2, sw
@@ -1892,8 +1885,7 @@ def dl_count(S: DeviceLevelState, plan: dict, roff, ranks, src, ncols: int, F1: 
     nslabs = (W + sw - 1) // sw
     acc16 = plan.get("accb", 4.0) == 2.0 and wword is None
     nacc = (C + 1) // 2 if acc16 else C
-    lds_k = n_used * (sw + 2) * 8 + ((nacc + 3) & ~3) * 4 + _slab_map_lds(F1)
-    n_wg = int(max(1, min(nslabs, 256 * min(max(1, TUNING.slab_lds_bytes // lds_k), 2))))
+    n_wg = _slab_workgroups(nslabs, n_used, sw, nacc, True, slab_map_lds(F1))
     _hip_call("fa_hip_count_slab_rec_cls", _p(roff), _p(ranks), _p(src), ncols, _p(item_map), F1, n_used,
               _p(plan.get("gpre")), _p(rec), 0, C, _p(wword), _p(out), sw, n_wg, None, 0, st, None,
               _p(S.ctl) + 8 * 221, 4 if acc16 else 0)

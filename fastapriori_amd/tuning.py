@@ -66,9 +66,6 @@ class Tuning:
     # gain: 70.6 -> 73.6 ms; the shard's size, not the level's: T40I10D100M's level 11
     # keeps ~20M rows and still gains, 21.8 -> 16.5 ms)
     window_trim_min_rows: int = 1 << 25
-    # bundle capacity = the largest over the slab widths (a bundle takes a narrower slab
-    # when that holds all of it) instead of the first width holding 8192 candidates
-    slab_cap_max: bool = False
     # bank-aware lane deal of device slab plans (levels.hip k_dl_lane_assign) from this many
     # rows (-1: off): ~0.18 ms per bundle against ~5 % of the slab counts (T10I4D100M
     # 42.1 -> 41.2 ms; the 12.5M-row shard 6.50 -> 6.85 ms, hence the threshold)

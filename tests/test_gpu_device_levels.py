@@ -247,3 +247,54 @@ def test_window_items_keep_counts(tune):
     assert st.get("device_multipass", 0) >= 1 and "fallbacks" not in st, st
     assert len(ref.levels) >= 6
     _same(got, ref)
+
+
+def _bundle_widths(miner, F1: int) -> list:
+    """(first level, levels, candidates, used items, slab width) of every device bundle
+    from the run's per-level metric records, each checked against the slab rule
+    (csrc/host/fa_slab.h through ops.primitives.slab_width) at the device loop's budget."""
+    import fastapriori_amd.ops.primitives as prim
+    recs = [r for r in miner.log.records if r.get("phase") == "level" and r["k"] >= 3]
+    assert recs and all(r.get("kernel") == "slab_rec_dev" for r in recs), recs
+    out = []
+    for k0 in sorted({r["bundled_with"] for r in recs}):
+        b = sorted((r for r in recs if r["bundled_with"] == k0), key=lambda r: r["k"])
+        assert [r["k"] for r in b] == list(range(k0, k0 + len(b)))
+        assert len({(r["slab_words"], r["used_items"]) for r in b}) == 1
+        C, n_used, sw = sum(r["candidates"] for r in b), b[0]["used_items"], b[0]["slab_words"]
+        want, cap = prim.slab_width(n_used, C, prim.dl_lds_budget(F1), 4)
+        assert sw == want and C <= cap, (k0, C, n_used, sw, want, cap)
+        out.append((k0, len(b), C, n_used, sw))
+    return out
+
+
+def test_bundle_slab_widths_follow_the_slab_rule(tune):
+    # every one-pass device bundle counts at the width the one rule gives for its used
+    # items and candidates, at the default LDS budget and at one shrunk on the CPU so that
+    # the first bundle (level 3's candidates and items, from F_2) leaves width 16
+    import fastapriori_amd.ops.primitives as prim
+    from fastapriori_amd.ops.host import apriori_gen
+    cpu = generate_shard(200_000, Comm(), "cpu", 10.0, 4.0, 2000, 1000, 4)
+    ref, _ = _mine(cpu, 0.002)
+    F1, g = len(ref.levels[0]), cpu.to(DEV)
+    f2 = np.ascontiguousarray(ref.levels[1], dtype=np.int32)
+    pi, eo, ex = apriori_gen(f2)
+    C3, U = int(ex.size), int(np.union1d(f2[pi].ravel(), ex).size)
+    # width 16 holds one candidate too few for min(C3, 8192): the rule moves on
+    shrunk = U * 144 + 4 * (min(C3, 8192) - 1)
+    sw3, cap3 = prim.slab_width(U, C3, shrunk, 4)
+    assert sw3 not in (0, 16) and cap3 >= C3, (U, C3, shrunk, sw3, cap3)
+    for budget in (None, shrunk + prim.slab_map_lds(F1)):
+        if budget is not None:
+            tune(slab_lds_bytes=budget)
+        m = FastApriori(0.002, config=MinerConfig(min_support=0.002), logger=Logger(0, enabled=False))
+        got = m.run(g)
+        assert "device_multipass" not in m.stats and m.stats.get("host_levels", 0) == 0, m.stats
+        bundles = _bundle_widths(m, F1)
+        # no level left out: the bundles cover levels 3 .. last
+        assert sum(b[1] for b in bundles) == m.stats["device_levels"] >= len(ref.levels) - 2
+        assert bundles[0][0] == 3 and bundles[0][3] == U and bundles[0][2] >= C3
+        print(f"slab_lds_bytes={TUNING.slab_lds_bytes}: bundles (k0, levels, C, used, sw) = {bundles}")
+        if budget is not None:
+            assert bundles[0][4] in (8, 4), bundles       # the shrunk budget did leave width 16
+        _same(got, ref)

@@ -260,7 +260,7 @@ def test_gen_chain_matches_iterated_gen():
     for a, b in zip(ff[1:], got):
         assert all(np.array_equal(x, y) for x, y in zip(a, b))
     used = np.unique(cand)
-    lim = ops.primitives.slab_total_limit(used.size)
+    lim = ops.primitives.slab_total_limit(used.size, ops.primitives.TUNING.slab_lds_bytes)
     assert sum(l[2].size for l in ff) <= max(lim, ff[0][2].size)
     c0 = got[0][2].size      # growth is measured against the previous level (the input for level 0)
     assert len(ops.primitives.apriori_gen_chain(cand, F1, DEV, 4, (c0 - 0.5) / cand.shape[0], 0, 1 << 40)) == 0
