@@ -18,6 +18,7 @@
 #include <cstdlib>
 
 #include "fa_hip.h"
+#include "../host/fa_dl.h"
 #include "../host/fa_slab.h"
 
 namespace fa {
@@ -1488,7 +1489,7 @@ __global__ __launch_bounds__(kSlabThreads) void k_count_slab_rec(
   constexpr int SWP = SW + 2;                       // row stride: odd number of 16-B slots
   constexpr int RS = SWP / 2;
   uint64_t* slab = reinterpret_cast<uint64_t*>(lds4);
-  // kAcc16 (flags & 8): two u16 counters per accumulator word (unit weights; twice the
+  // kAcc16 (flags & kSlabFlagAcc16): two u16 counters per accumulator word (unit weights; twice the
   // candidates per accumulator pass), drained into the u32 global counts before they can
   // carry: a slab adds at most SW * 64 to a counter.  A template parameter: a runtime
   // flag put a scalar branch pair around every accumulator add of the extension loop.
@@ -1508,10 +1509,11 @@ __global__ __launch_bounds__(kSlabThreads) void k_count_slab_rec(
   const int64_t W = (ncols + 63) >> 6;
   const int64_t nslabs = (W + SW - 1) / SW;
   const int4 z4 = make_int4(0, 0, 0, 0);
-  // candidate distribution (flags bits 8-15: this rank, 16-23: ranks - 1): the rank counts
+  // candidate distribution (flags: kSlabFlagPartShift this rank, kSlabFlagNpartsShift ranks - 1): the rank counts
   // the 64-piece chunks part, part + nparts, ... over all rows, one chunk per wave step, so
   // a wave still walks 64 consecutive records (the lane deal stays valid)
-  const int ppart = (flags >> 8) & 0xFF, npart = ((flags >> 16) & 0xFF) + 1;
+  const int ppart = (flags >> kSlabFlagPartShift) & kSlabFlagPartMask;
+  const int npart = ((flags >> kSlabFlagNpartsShift) & kSlabFlagPartMask) + 1;
   const int gstep = kSlabThreads * npart;
   const int g0 = (ppart + npart * (int)(threadIdx.x >> 6)) * 64 + (int)(threadIdx.x & 63);
   int4 ra = z4, rb = z4, rc = z4;
@@ -1683,9 +1685,9 @@ __global__ __launch_bounds__(kSlabThreads) void k_count_slab_rec(
         if (j < m) and_row(p, pr[j]);
       }
       }
-      // an all-zero prefix skips its extensions; dense levels (flags & 4: every frequent
+      // an all-zero prefix skips its extensions; dense levels (flags & kSlabFlagDense: every frequent
       // prefix expects >= 4 rows per slab) skip the test instead (32 VALU ops per piece at SW = 16)
-      uint32_t any = flags & 4;
+      uint32_t any = flags & kSlabFlagDense;
       if (!any) {
 #pragma unroll
         for (int q = 0; q < SW / 2; ++q) any |= p[q].x | p[q].y | p[q].z | p[q].w;
@@ -2035,10 +2037,10 @@ FA_API int fa_hip_win_compact(const uint64_t* bm, int64_t ld, const int32_t* row
 // and the slab is built from contiguous rows.  Returns 3 when that exceeds the LDS.
 // g_dev (optional): the piece count read by the kernel from device memory (G is then
 // ignored; device-planned bundles, levels.hip fa_hip_dl_plan).
-// cls bit 0: the records carry class-layout flags (plan.cpp cls_layout): unit weights
-// run k_count_slab_rec<.., kCls> (the flags are hints: the plain kernel ignores them and
-// recomputes every prefix, with the same counts).  cls bit 1: dense level, no
-// all-zero-prefix test (the counts are the same either way).  cls bit 2: u16 packed
+// cls (fa_dl.h) kSlabCls: the records carry class-layout flags (plan.cpp cls_layout): unit
+// weights run k_count_slab_rec<.., kCls> (the flags are hints: the plain kernel ignores them
+// and recomputes every prefix, with the same counts).  kSlabDense: dense level, no
+// all-zero-prefix test (the counts are the same either way).  kSlabAcc16: u16 packed
 // accumulators (unit weights: half the LDS per candidate, drained every 65535 / (SW * 64)
 // slabs).
 // Test hook: at most this many workgroups per slab count (0: no cap).  One workgroup
@@ -2048,7 +2050,7 @@ static int g_slab_max_wg = 0;
 FA_API void fa_hip_debug_slab_max_wg(int n) { g_slab_max_wg = n; }
 // Candidate distribution of the slab counts launched next (fastapriori_amd
 // FastApriori._piece_part with --strategy candidate): this rank counts the 64-piece
-// chunks part, part + nparts, ... (k_count_slab_rec flags bits 8-23); (0, 1): every piece.
+// chunks part, part + nparts, ... (k_count_slab_rec flags, kSlabFlagPartShift on); (0, 1): every piece.
 static int g_piece_part = 0, g_piece_nparts = 1;
 FA_API int fa_hip_set_piece_part(int part, int nparts) {
   if (nparts < 1 || nparts > 256 || part < 0 || part >= nparts) return 1;
@@ -2065,8 +2067,8 @@ FA_API int fa_hip_count_slab_rec_cls(const int64_t* roff, const int32_t* ranks, 
   if ((G <= 0 && !g_dev) || C <= 0 || ncols <= 0) return 0;
   // the class-layout flags name a thread's previous piece in the undivided plan: with the
   // pieces divided among ranks the plain kernel recomputes every prefix instead
-  if (g_piece_nparts > 1) cls &= ~1;
-  const bool acc16 = (cls & 4) && !wword;   // two u16 counters per accumulator word
+  if (g_piece_nparts > 1) cls &= ~kSlabCls;
+  const bool acc16 = (cls & kSlabAcc16) && !wword;   // two u16 counters per accumulator word
   const int64_t n_acc = acc16 ? (C + 1) / 2 : C;
   const bool contig = !bm && !src;
   const size_t lds = (size_t)slab_kernel_lds(n_used, sw, slab_acc_words(n_acc), contig ? slab_map_lds(F1) : 0);
@@ -2078,10 +2080,10 @@ FA_API int fa_hip_count_slab_rec_cls(const int64_t* roff, const int32_t* ranks, 
   KernT kern = nullptr;
 #define FA_REC_MODE(S, B)                                                                              \
   kern = wword ? (KernT)k_count_slab_rec<S, true, B>                                                   \
-         : (cls & 1) ? (acc16 ? (KernT)k_count_slab_rec<S, false, B, true, true>                       \
-                              : (KernT)k_count_slab_rec<S, false, B, true, false>)                      \
-                     : (acc16 ? (KernT)k_count_slab_rec<S, false, B, false, true>                      \
-                              : (KernT)k_count_slab_rec<S, false, B, false, false>);
+         : (cls & kSlabCls) ? (acc16 ? (KernT)k_count_slab_rec<S, false, B, true, true>                \
+                                     : (KernT)k_count_slab_rec<S, false, B, true, false>)              \
+                            : (acc16 ? (KernT)k_count_slab_rec<S, false, B, false, true>               \
+                                     : (KernT)k_count_slab_rec<S, false, B, false, false>);
 #define FA_REC_CASE(S)                                    \
   if (sw == S) {                                          \
     if (bm) { FA_REC_MODE(S, kBuildBM) }                  \
@@ -2096,19 +2098,11 @@ FA_API int fa_hip_count_slab_rec_cls(const int64_t* roff, const int32_t* ranks, 
 #undef FA_REC_MODE
   if (!kern) return 1;
   (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  const int flags = ((cls & 2) ? 4 : 0) | (acc16 ? 8 : 0) | (g_piece_part << 8) | ((g_piece_nparts - 1) << 16);
+  const int flags = ((cls & kSlabDense) ? kSlabFlagDense : 0) | (acc16 ? kSlabFlagAcc16 : 0) |
+                    (g_piece_part << kSlabFlagPartShift) | ((g_piece_nparts - 1) << kSlabFlagNpartsShift);
   hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(kSlabThreads), lds, st, roff, ranks, src, ncols, item_map, F1,
                      n_used, gpre, (const int4*)rec, G, C, wword, out, bm, Wp, bm_rows, flags, g_dev);
   FA_LAUNCH_RET();
-}
-
-FA_API int fa_hip_count_slab_rec(const int64_t* roff, const int32_t* ranks, const int32_t* src, int64_t ncols,
-                                 const int32_t* item_map, int F1, int n_used, const int32_t* gpre, const void* rec,
-                                 int G, int C, const int32_t* wword, uint32_t* out, int sw, int n_wg,
-                                 const uint64_t* bm, int64_t Wp, hipStream_t st, const int32_t* bm_rows,
-                                 const int32_t* g_dev) {
-  return fa_hip_count_slab_rec_cls(roff, ranks, src, ncols, item_map, F1, n_used, gpre, rec, G, C, wword, out, sw,
-                                   n_wg, bm, Wp, st, bm_rows, g_dev, 0);
 }
 
 FA_API int fa_hip_block_counts(const int64_t* roff, const int32_t* ranks, int64_t T, int32_t F1, uint8_t* cnt,

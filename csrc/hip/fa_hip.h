@@ -96,4 +96,17 @@ __device__ __forceinline__ uint32_t xcd_remap(uint32_t orig, uint32_t nwg) {
   return base + orig / nx;
 }
 
+struct DlDesc;   // ../host/fa_dl.h
+
 }  // namespace fa
+
+// Launchers called across files (the bundle post step, gen.hip dl_post): the device
+// piece plan (levels.hip) and the slab count (count.hip; cls: fa_dl.h kSlab* bits)
+FA_API int fa_hip_dl_plan(const fa::DlDesc* desc, int L, long long* ctl, int F1, int32_t* item_map, void* rec,
+                          int64_t max_pieces, int32_t* part, int64_t part_cap, int32_t* gpre, int64_t gpre_cap,
+                          int sw, hipStream_t st);
+FA_API int fa_hip_count_slab_rec_cls(const int64_t* roff, const int32_t* ranks, const int32_t* src, int64_t ncols,
+                                     const int32_t* item_map, int F1, int n_used, const int32_t* gpre,
+                                     const void* rec, int G, int C, const int32_t* wword, uint32_t* out, int sw,
+                                     int n_wg, const uint64_t* bm, int64_t Wp, hipStream_t st,
+                                     const int32_t* bm_rows, const int32_t* g_dev, int cls);

@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "fa_hip.h"
+#include "../host/fa_dl.h"
 #include "../host/fa_slab.h"
 
 namespace fa {
@@ -211,7 +212,6 @@ __global__ __launch_bounds__(256) void k_ag_rows(const int32_t* __restrict__ P, 
 
 // bitset words per lane for nw words: 1, 2, 4 or 8 (F1 <= 32768)
 static inline int ag_nwl(int nw) { return nw <= 64 ? 1 : nw <= 128 ? 2 : nw <= 256 ? 4 : 8; }
-constexpr int kAgMaxF1 = 64 * 64 * 8;
 // u32 words of a chain's used-item bitset (ops.primitives.ag_mark_words mirrors this)
 static inline int ag_mark_words(int F1) { return std::max(128, (F1 + 31) / 32); }
 // LAUNCH(N) for the lane width N of nw bitset words
@@ -467,8 +467,7 @@ FA_API int fa_hip_ag_chain(const int32_t* P0, int64_t n0, int m0, int F1, void* 
 // enqueued in batches of kAgdBatch with one control-block readback per batch,
 // then the accepted levels are copied out.  (A single cooperative kernel was
 // measured slower: its grid barriers cost more than these kernel boundaries.)
-//   ctl (device int64): 0 stop, 1 accepted levels (incl. level 0), 2 total,
-//   3 last C, 4 tmax, 8 + l: n_l (input rows of level l), 40 + l: C_l.
+// The control block is the first kDlGl words of fa_dl.h's (slot 4: kDlTmax).
 // ---------------------------------------------------------------------------
 namespace fa {
 
@@ -480,12 +479,12 @@ __global__ void k_agd_setup(long long* __restrict__ c, int64_t n1, int64_t total
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   int64_t n_used = 0;
   for (int q = 0; q < MW; ++q) n_used += __popc(mark[q]);
-  c[0] = total > slab_cap(n_used, total, lds, 4.0) ? 1 : 0;   // level k alone needs several passes
-  c[1] = 1;
-  c[2] = total;
-  c[3] = last;
-  c[4] = slab_total_limit(n_used, lds, 4.0);
-  c[9] = n1;
+  c[kDlStop] = total > slab_cap(n_used, total, lds, 4.0) ? 1 : 0;   // level k alone needs several passes
+  c[kDlLevels] = 1;
+  c[kDlTotal] = total;
+  c[kDlLastC] = last;
+  c[kDlTmax] = slab_total_limit(n_used, lds, 4.0);
+  c[kDlNl + 1] = n1;
 }
 
 // clear the hash tables (-1) and Ext bitsets (0) of a batch of levels: region q is
@@ -498,7 +497,7 @@ struct AgdClear {
 };
 
 __global__ __launch_bounds__(256) void k_agd_clear(AgdClear A, const long long* __restrict__ c) {
-  if (c[0]) return;
+  if (c[kDlStop]) return;
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (int q = 0; q < A.nreg; ++q)
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < A.len[q]; i += stride) A.p[q][i] = A.val[q];
@@ -506,8 +505,8 @@ __global__ __launch_bounds__(256) void k_agd_clear(AgdClear A, const long long* 
 
 __global__ __launch_bounds__(256) void k_agd_insert(const int32_t* __restrict__ P, int m, int32_t* __restrict__ table,
                                                     uint32_t mask, const long long* __restrict__ c, int l) {
-  if (c[0]) return;
-  const int64_t n = c[8 + l];
+  if (c[kDlStop]) return;
+  const int64_t n = c[kDlNl + l];
   // grid-stride (the grid is sized for the level's bound, capped: a stopped chain's
   // launches then cost a few workgroups each)
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -527,8 +526,8 @@ __global__ __launch_bounds__(256) void k_agd_ext(const int32_t* __restrict__ P, 
                                                  const int32_t* __restrict__ table, uint32_t mask, int nw,
                                                  unsigned long long* __restrict__ ext, const long long* __restrict__ c,
                                                  int l) {
-  if (c[0]) return;
-  const int64_t n = c[8 + l];
+  if (c[kDlStop]) return;
+  const int64_t n = c[kDlNl + l];
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const int32_t* r = P + i * m;
     const int32_t s = ag_find(P, m, table, mask, r, m - 1);
@@ -545,8 +544,8 @@ __global__ __launch_bounds__(256) void k_agd_rows(const int32_t* __restrict__ P,
                                                   const unsigned long long* __restrict__ ext, int32_t* __restrict__ cnt,
                                                   const int64_t* __restrict__ off, int32_t* __restrict__ rows,
                                                   const long long* __restrict__ c, int l) {
-  if (c[0]) return;
-  const int64_t n = c[8 + l];
+  if (c[kDlStop]) return;
+  const int64_t n = c[kDlNl + l];
   const int lane = threadIdx.x & 63;
   const int64_t nwave = (int64_t)gridDim.x * (blockDim.x / 64);
   for (int64_t i = (int64_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6); i < n; i += nwave) {
@@ -568,8 +567,8 @@ __global__ __launch_bounds__(1024) void k_agd_scan_decide(const int32_t* __restr
                                                           int64_t c_bound) {
   __shared__ int64_t part[16];
   __shared__ int64_t carry;
-  if (c[0]) return;
-  const int64_t n = c[8 + l];
+  if (c[kDlStop]) return;
+  const int64_t n = c[kDlNl + l];
   if (threadIdx.x == 0) { carry = 0; off[0] = 0; }
   __syncthreads();
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -588,13 +587,16 @@ __global__ __launch_bounds__(1024) void k_agd_scan_decide(const int32_t* __restr
   }
   if (threadIdx.x != 0) return;
   const int64_t C = carry;
-  const int64_t total = c[2], last = c[3], tmax = c[4];
-  if (C == 0 || (double)C > growth * (double)last || total + C > tmax || C > c_bound) { c[0] = 1; return; }
-  c[40 + l] = C;
-  c[1] = l + 1;
-  c[2] = total + C;
-  c[3] = C;
-  c[8 + l + 1] = C;
+  const int64_t total = c[kDlTotal], last = c[kDlLastC], tmax = c[kDlTmax];
+  if (C == 0 || (double)C > growth * (double)last || total + C > tmax || C > c_bound) {
+    c[kDlStop] = 1;
+    return;
+  }
+  c[kDlCl + l] = C;
+  c[kDlLevels] = l + 1;
+  c[kDlTotal] = total + C;
+  c[kDlLastC] = C;
+  c[kDlNl + l + 1] = C;
 }
 
 }  // namespace fa
@@ -609,18 +611,18 @@ static int ag_chain_dev(const int32_t* P1, int64_t n1, int m1, int nw, char* w0,
   using namespace fa;
   auto al = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
   const int LM = std::min(max_levels - 1, kAgdMaxLevels - 2);
-  long long* c = reinterpret_cast<long long*>(w); w += al(8 * 72);
+  long long* c = reinterpret_cast<long long*>(w); w += al(8 * kDlGl);
   const int64_t acc_max = (int64_t)(lds / 4);         // no bundle total passes the accumulator capacity
   struct Lv { int32_t* cnt; int32_t* rows; int m; };
   Lv lv[kAgdMaxLevels];
   int64_t nb = n1;
   int m = m1;
   const int32_t* P = P1;
-  long long ch[72];
-  ch[0] = LM <= 0;
-  ch[1] = 1;
+  long long ch[kDlGl];
+  ch[kDlStop] = LM <= 0;
+  ch[kDlLevels] = 1;
   hipLaunchKernelGGL(k_agd_setup, dim3(1), dim3(64), 0, st, c, n1, total, last, mark, MW, lds);
-  for (int l0 = 1; l0 <= LM && !ch[0]; l0 += kAgdBatch) {
+  for (int l0 = 1; l0 <= LM && !ch[kDlStop]; l0 += kAgdBatch) {
     const int l1 = std::min(LM, l0 + kAgdBatch - 1);
     struct Bufs { int32_t* table; uint32_t cap; unsigned long long* ext; int64_t* off; int64_t nb, cb; };
     Bufs bf[kAgdBatch];
@@ -672,9 +674,9 @@ static int ag_chain_dev(const int32_t* P1, int64_t n1, int m1, int nw, char* w0,
     (void)hipMemcpyAsync(ch, c, sizeof(ch), hipMemcpyDeviceToHost, st);
     if (hipStreamSynchronize(st) != hipSuccess) return 7;
   }
-  const int L = (int)ch[1];
+  const int L = (int)ch[kDlLevels];
   for (int l = 1; l < L; ++l) {
-    const int64_t n = ch[8 + l], C = ch[40 + l];
+    const int64_t n = ch[kDlNl + l], C = ch[kDlCl + l];
     const int ml = lv[l].m;
     const int64_t need_host = hoff + n + C + C * (ml + 1);
     if (need_host > host_cap) { (void)hipStreamSynchronize(st); sizes[1] = 2 * need_host; return 6; }
@@ -702,19 +704,9 @@ static int ag_chain_dev(const int32_t* P1, int64_t n1, int m1, int nw, char* w0,
 // acceptance of ag_chain_dev, without copying any level out.  Planning
 // (levels.hip fa_hip_dl_plan), counting and thresholding (fa_hip_dl_threshold)
 // then run on the same stream.
-//   ctl (device int64 [kDlCtl]): 0 stop  1 accepted levels  2 total  3 last C
-//     5 multi (level 0 needs several accumulator passes: host path)  6 n_used
-//     7 end (|F_{k-1}| < k or C_0 = 0: mining is over)  8 + l: n_l  40 + l: C_l
-//     72 + l: G_l (parent rows with >= 1 candidate: the reference's group count)
-//     104 (kDlEmpty): the chain stopped on a speculative level with no candidates
-//     512 .. 1023: used-item bitset of level 0 (kDlBitsW words: F1 <= 32768 bits)
+// The control block ctl, the level table desc and the post step's DlPost: fa_dl.h.
 // ---------------------------------------------------------------------------
 namespace fa {
-
-constexpr int kDlCtl = 1024;
-constexpr int kDlBits = 512;       // first word of the used-item bitset in ctl
-constexpr int kDlBitsW = 512;      // its 64-bit words (F1 <= kAgMaxF1 = 32768)
-constexpr int kDlEmpty = 104;      // 1: the chain stopped on a level without candidates
 
 __device__ int64_t agd_block_scan(const int32_t* __restrict__ cnt, int64_t* __restrict__ off, int64_t n,
                                   int64_t* groups = nullptr) {
@@ -746,7 +738,7 @@ __device__ int64_t agd_block_scan(const int32_t* __restrict__ cnt, int64_t* __re
   return carry;
 }
 
-// ctl[4] = 1: the device row count n_src[0] exceeds n_bound (the buffers' size):
+// ctl[kDlOverBound] = 1: the device row count n_src[0] exceeds n_bound (the buffers' size):
 // nothing runs and the host raises
 __global__ __launch_bounds__(kDlCtl) void k_dl_setup0(long long* __restrict__ c, const long long* __restrict__ n_src,
                                                       int64_t n_const, int kmin, int64_t n_bound) {
@@ -754,10 +746,10 @@ __global__ __launch_bounds__(kDlCtl) void k_dl_setup0(long long* __restrict__ c,
   __syncthreads();
   if (threadIdx.x == 0) {
     const int64_t n = n_src ? (int64_t)n_src[0] : n_const;
-    if (n > n_bound) { c[4] = 1; c[0] = 1; return; }
-    c[8] = n;
-    c[7] = n < kmin ? 1 : 0;       // the reference's loop test |F_{k-1}| >= k (FastApriori.scala:111)
-    c[0] = c[7];
+    if (n > n_bound) { c[kDlOverBound] = 1; c[kDlStop] = 1; return; }
+    c[kDlNl] = n;
+    c[kDlEnd] = n < kmin ? 1 : 0;   // the reference's loop test |F_{k-1}| >= k (FastApriori.scala:111)
+    c[kDlStop] = c[kDlEnd];
   }
 }
 
@@ -765,15 +757,15 @@ __global__ __launch_bounds__(kDlCtl) void k_dl_setup0(long long* __restrict__ c,
 // one accumulator pass) marks it "multi" (host path); C_0 = 0 ends the mining
 __global__ __launch_bounds__(1024) void k_dl_decide0(const int32_t* __restrict__ cnt, int64_t* __restrict__ off,
                                                       long long* __restrict__ c, int64_t c_bound) {
-  if (c[0]) return;
+  if (c[kDlStop]) return;
   int64_t g = 0;
-  const int64_t C = agd_block_scan(cnt, off, c[8], &g);
+  const int64_t C = agd_block_scan(cnt, off, c[kDlNl], &g);
   if (threadIdx.x != 0) return;
-  c[40] = C;
-  c[72] = g;
-  if (C == 0) { c[7] = 1; c[0] = 1; return; }
-  if (C > c_bound) { c[5] = 1; c[0] = 1; return; }
-  c[1] = 1; c[2] = C; c[3] = C; c[9] = C;
+  c[kDlCl] = C;
+  c[kDlGl] = g;
+  if (C == 0) { c[kDlEnd] = 1; c[kDlStop] = 1; return; }
+  if (C > c_bound) { c[kDlMulti] = 1; c[kDlStop] = 1; return; }
+  c[kDlLevels] = 1; c[kDlTotal] = C; c[kDlLastC] = C; c[kDlNl + 1] = C;
 }
 
 // Level 0's scan over many workgroups when F_{k-1} is large (T40I10D100M's bundles start
@@ -786,8 +778,8 @@ constexpr int kDsBlk = 4096;
 __global__ __launch_bounds__(1024) void k_ds_blocks(const int32_t* __restrict__ cnt, int64_t* __restrict__ off,
                                                     const long long* __restrict__ c, int64_t* __restrict__ bs,
                                                     int nblk) {
-  if (c[0]) return;
-  const int64_t n = c[8];
+  if (c[kDlStop]) return;
+  const int64_t n = c[kDlNl];
   const int64_t b0 = (int64_t)blockIdx.x * kDsBlk;
   if (b0 >= n) {
     if (threadIdx.x == 0) { bs[blockIdx.x] = 0; bs[nblk + blockIdx.x] = 0; }
@@ -828,7 +820,7 @@ __global__ __launch_bounds__(1024) void k_ds_blocks(const int32_t* __restrict__ 
 
 __global__ __launch_bounds__(1024) void k_ds_decide0(int64_t* __restrict__ off, long long* __restrict__ c,
                                                      int64_t* __restrict__ bs, int nblk, int64_t c_bound) {
-  if (c[0]) return;
+  if (c[kDlStop]) return;
   __shared__ int64_t part[16];
   __shared__ int64_t carry, gz;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -858,19 +850,19 @@ __global__ __launch_bounds__(1024) void k_ds_decide0(int64_t* __restrict__ off, 
   }
   if (threadIdx.x != 0) return;
   const int64_t C = carry;
-  c[40] = C;
-  c[72] = gz;
-  if (C == 0) { c[7] = 1; c[0] = 1; return; }
-  if (C > c_bound) { c[5] = 1; c[0] = 1; return; }
-  c[1] = 1; c[2] = C; c[3] = C; c[9] = C;
+  c[kDlCl] = C;
+  c[kDlGl] = gz;
+  if (C == 0) { c[kDlEnd] = 1; c[kDlStop] = 1; return; }
+  if (C > c_bound) { c[kDlMulti] = 1; c[kDlStop] = 1; return; }
+  c[kDlLevels] = 1; c[kDlTotal] = C; c[kDlLastC] = C; c[kDlNl + 1] = C;
 }
 
 __global__ __launch_bounds__(1024) void k_ds_add(int64_t* __restrict__ off, const long long* __restrict__ c,
                                                  const int64_t* __restrict__ bs, int nblk) {
-  // after k_ds_decide0: a multi / empty level 0 (c[0] set) is regenerated or ends, its
-  // offsets unused; c[8] and the block bases are final either way
-  if (c[4]) return;                                     // n past the buffers' bound: nothing ran
-  const int64_t n = c[8];
+  // after k_ds_decide0: a multi / empty level 0 (kDlStop set) is regenerated or ends, its
+  // offsets unused; n_0 and the block bases are final either way
+  if (c[kDlOverBound]) return;                          // n past the buffers' bound: nothing ran
+  const int64_t n = c[kDlNl];
   const int64_t b0 = (int64_t)blockIdx.x * kDsBlk;
   if (b0 >= n || blockIdx.x == 0) return;               // block 0's base is 0
   const int64_t base = bs[2 * nblk + blockIdx.x];
@@ -885,10 +877,10 @@ __global__ __launch_bounds__(1024) void k_ds_add(int64_t* __restrict__ off, cons
 __global__ __launch_bounds__(256) void k_dl_mark(const int32_t* __restrict__ rows, int m1,
                                                  long long* __restrict__ c, int w32) {
   __shared__ uint32_t lb[2 * kDlBitsW];
-  if (c[0] && !c[5]) return;         // (a multi level still reports its used items)
+  if (c[kDlStop] && !c[kDlMulti]) return;   // (a multi level still reports its used items)
   for (int q = threadIdx.x; q < w32; q += 256) lb[q] = 0u;
   __syncthreads();
-  const int64_t n = c[5] ? 0 : c[40] * (int64_t)m1;
+  const int64_t n = c[kDlMulti] ? 0 : c[kDlCl] * (int64_t)m1;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
     atomicOr(&lb[rows[i] >> 5], 1u << (rows[i] & 31));
   __syncthreads();
@@ -905,8 +897,11 @@ __global__ __launch_bounds__(64) void k_dl_post0(long long* __restrict__ c, doub
   for (int q = threadIdx.x; q < w32; q += 64) part += __popc(mk[q]);
   const int64_t n_used = (int64_t)wave_sum_u32(part);
   if (threadIdx.x != 0) return;
-  c[6] = n_used;
-  if (c[1] == 1 && c[40] > slab_cap(n_used, c[40], lds, accb)) { c[5] = 1; c[0] = 1; }
+  c[kDlNUsed] = n_used;
+  if (c[kDlLevels] == 1 && c[kDlCl] > slab_cap(n_used, c[kDlCl], lds, accb)) {
+    c[kDlMulti] = 1;
+    c[kDlStop] = 1;
+  }
 }
 
 // acceptance of speculative level l >= 1 (same rule as k_agd_scan_decide, with the
@@ -914,25 +909,25 @@ __global__ __launch_bounds__(64) void k_dl_post0(long long* __restrict__ c, doub
 __global__ __launch_bounds__(1024) void k_dl_decide(const int32_t* __restrict__ cnt, int64_t* __restrict__ off,
                                                      long long* __restrict__ c, int l, double growth, int64_t c_bound,
                                                      double lds, double accb) {
-  if (c[0]) return;
+  if (c[kDlStop]) return;
   int64_t g = 0;
-  const int64_t C = agd_block_scan(cnt, off, c[8 + l], &g);
+  const int64_t C = agd_block_scan(cnt, off, c[kDlNl + l], &g);
   if (threadIdx.x != 0) return;
-  const int64_t total = c[2], last = c[3];
+  const int64_t total = c[kDlTotal], last = c[kDlLastC];
   if (C == 0 || (double)C > growth * (double)last || C > c_bound ||
-      total + C > slab_cap(c[6], total + C, lds, accb)) {
-    c[0] = 1;
+      total + C > slab_cap(c[kDlNUsed], total + C, lds, accb)) {
+    c[kDlStop] = 1;
     // no candidates even from the previous level's candidates (a superset of its
     // frequent rows): the mining ends with this bundle (the host skips the next one)
     if (C == 0) c[kDlEmpty] = 1;
     return;
   }
-  c[40 + l] = C;
-  c[72 + l] = g;
-  c[1] = l + 1;
-  c[2] = total + C;
-  c[3] = C;
-  c[8 + l + 1] = C;
+  c[kDlCl + l] = C;
+  c[kDlGl + l] = g;
+  c[kDlLevels] = l + 1;
+  c[kDlTotal] = total + C;
+  c[kDlLastC] = C;
+  c[kDlNl + l + 1] = C;
 }
 
 // Speculative level l >= 2 of a device bundle with the next level's structures fused
@@ -952,8 +947,8 @@ __global__ __launch_bounds__(256) void k_dl_rows(const int32_t* __restrict__ P, 
                                                  const int64_t* __restrict__ off, int32_t* __restrict__ rows,
                                                  const long long* __restrict__ c, int l, int32_t* __restrict__ ntab,
                                                  uint32_t ncap, unsigned long long* __restrict__ next_ext) {
-  if (c[0]) return;
-  const int64_t n = c[8 + l];
+  if (c[kDlStop]) return;
+  const int64_t n = c[kDlNl + l];
   if (!kEmit && ntab) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < (int64_t)ncap; q += stride) ntab[q] = -1;
@@ -993,7 +988,7 @@ __global__ __launch_bounds__(256) void k_dl_rows(const int32_t* __restrict__ P, 
 // into the front of ws; with sync, ONE synchronisation copies ctl to ctl_host
 // (without it the caller queues fa_hip_dl_more and reads everything once).
 // c_bound: the largest C_0 the level may have (one accumulator pass); a larger
-// level is reported as multi (ctl[5]) without its rows.  lds: LDS bytes the slab
+// level is reported as multi (ctl[kDlMulti]) without its rows.  lds: LDS bytes the slab
 // kernel has for slab + accumulators; accb: bytes per accumulator (4, or 2: u16).  info (int64 out): 0 ws bytes used,
 // 1 cnt (ext ids at cnt + n), 2 off, 3 candidate rows [C_0][m0 + 1].
 // Returns 0, 1 (bad arguments) or 5 (ws too small: info[0] = bytes needed).
@@ -1065,63 +1060,21 @@ FA_API int fa_hip_dl_level0(const int32_t* P0, const long long* n_src, int64_t n
 // the control block into one of two pinned mirrors.  The next batch is queued
 // before the host waits on the previous one, so the GPU does not idle while the
 // host reads a batch's acceptance; levels of a stopped chain exit at once.  One
-// final synchronisation copies ctl to ctl_host.  ws + ws_used is free; desc (int64
-// [32][8], host) holds level 0's pointers and m on entry (rows 0..3 and 4) and
-// receives every accepted level l:
-//   0 parent rows P_l  1 cnt (ext ids at cnt + n_l)  2 off  3 candidate rows
-//   4 m_l (parent row length)  5 n_l  6 C_l  7 base (candidates of levels < l)
-// Returns 0 (ctl_host[1] = accepted levels incl. level 0), 5 (ws too small:
-// info[0] = bytes needed) or 7.
-//
-// post (optional, host DlPost): right after the synchronisation, with no return to
-// the host interpreter in between, the bundle's device piece plan is queued
-// (levels.hip fa_hip_dl_plan), the transaction-trimming decision is taken
-// (FastApriori._trim_worth_it, the same binomial estimate), and when no trim is
-// due the slab count itself is queued (count.hip fa_hip_count_slab_rec): the GPU
-// then counts while the host does its bookkeeping.  post->done: 0 nothing queued
-// (stopped chain, multi-pass level, buffers too small), 1 planned (the caller trims,
-// then counts), 2 planned and counted into post->out.
-struct DlPost {
-  // plan buffers (grow-only, the caller's): item_map int32 [F1], rec int4 [3 * rec_cap],
-  // part int32 [part_cap], out uint32 [out_cap]
-  int32_t* item_map; void* rec; int32_t* part; uint32_t* out;
-  int64_t rec_cap, part_cap, out_cap;
-  // the count's rows and LDS budget
-  const int64_t* roff; const int32_t* ranks; const int32_t* src; const int32_t* wword;
-  int64_t ncols; double lds_kernel; double lds_budget;
-  // trimming decision (trim_ok = 0: never): c1 int64 [F1] item supports, alive uint8 [F1],
-  // len_hist int64 [256] (nullptr: decided by the caller), T rows, nnz, min rows, level k
-  const int64_t* c1; const uint8_t* alive; const int64_t* len_hist;
-  int64_t T, nnz, trim_min_rows, trim_ok, k;
-  // out
-  int64_t done, sw, cap, n_wg, C, trim;
-  // prefix slab rows of levels with prefixes past 12 ids (levels.hip gpre), int32 [gpre_cap]
-  int32_t* gpre; int64_t gpre_cap;
-  // LDS bytes per accumulator: 4, or 2 (unit weights: count.hip's packed u16 counters)
-  double accb;
-  // trim when the estimate keeps fewer than this share of the rows, or of the items
-  // (FastApriori._trim_worth_it, TUNING.trim_rows_frac / trim_nnz_frac)
-  double trim_rows_frac, trim_nnz_frac;
-};
-static_assert(sizeof(DlPost) == 33 * 8, "DlPost layout (ops.primitives.DlPostC)");
-
-FA_API int fa_hip_dl_plan(const int64_t* desc, int L, long long* ctl, int F1, int32_t* item_map, void* rec,
-                          int64_t max_pieces, int32_t* part, int64_t part_cap, int32_t* gpre, int64_t gpre_cap,
-                          int sw, hipStream_t st);
-FA_API int fa_hip_count_slab_rec_cls(const int64_t* roff, const int32_t* ranks, const int32_t* src, int64_t ncols,
-                                     const int32_t* item_map, int F1, int n_used, const int32_t* gpre,
-                                     const void* rec, int G, int C, const int32_t* wword, uint32_t* out, int sw,
-                                     int n_wg, const uint64_t* bm, int64_t Wp, hipStream_t st,
-                                     const int32_t* bm_rows, const int32_t* g_dev, int cls);
-
-static void dl_post(DlPost* P, const int64_t* desc, int L, long long* ctl, const long long* ch, int F1,
+// final synchronisation copies ctl to ctl_host.  ws + ws_used is free; desc (host
+// DlDesc [kDlMaxL]) holds level 0's pointers and m on entry (P .. m) and receives
+// every accepted level.
+// Returns 0 (ctl_host[kDlLevels] = accepted levels incl. level 0), 5 (ws too small:
+// info[0] = bytes needed) or 7.  post (optional, host DlPost, fa_dl.h): the bundle's
+// plan, trimming decision and count, queued right after the synchronisation.
+static void dl_post(DlPost* P, const DlDesc* desc, int L, long long* ctl, const long long* ch, int F1,
                     hipStream_t st) {
   P->done = 0;
-  if (ch[0] && ch[1] == 0) return;                 // nothing accepted
-  if (ch[4] || ch[5] || ch[7] || L < 1) return;    // bound error, multi-pass level, end of mining
+  if (ch[kDlStop] && ch[kDlLevels] == 0) return;   // nothing accepted
+  // bound error, multi-pass level, end of mining
+  if (ch[kDlOverBound] || ch[kDlMulti] || ch[kDlEnd] || L < 1) return;
   int64_t C = 0, R = 0;
-  for (int l = 0; l < L; ++l) { C += desc[8 * l + 6]; R += desc[8 * l + 5]; }
-  const int64_t n_used = ch[6];
+  for (int l = 0; l < L; ++l) { C += desc[l].C; R += desc[l].n; }
+  const int64_t n_used = ch[kDlNUsed];
   P->C = C;
   if (C < 1 || C > P->rec_cap || C > P->out_cap || 8 * ((R + 255) / 256) > P->part_cap) return;
   // slab width (fa_slab.h), one accumulator pass
@@ -1163,27 +1116,26 @@ static void dl_post(DlPost* P, const int64_t* desc, int L, long long* ctl, const
                             slab_kernel_lds(n_used, sw, slab_acc_words(nacc), slab_map_lds(F1)));
   if (fa_hip_count_slab_rec_cls(P->roff, P->ranks, P->src, P->ncols, P->item_map, F1, (int)n_used, P->gpre, P->rec,
                                 0, (int)C, P->wword, P->out, sw, (int)P->n_wg, nullptr, 0, st, nullptr,
-                                reinterpret_cast<const int32_t*>(ctl + 221), acc16 ? 4 : 0) != 0)
+                                reinterpret_cast<const int32_t*>(ctl + kDlPiecesI32), acc16 ? kSlabAcc16 : 0) != 0)
     return;
   P->done = 2;
 }
 
 FA_API int fa_hip_dl_more(int F1, void* ws, int64_t ws_bytes, int64_t ws_used, long long* ctl, long long* ctl_host,
-                          double growth, int max_levels, double lds, double accb, int64_t n1_bound, int64_t* desc,
-                          int64_t* info,
-                          hipStream_t st, void* post) {
+                          double growth, int max_levels, double lds, double accb, int64_t n1_bound, fa::DlDesc* desc,
+                          int64_t* info, hipStream_t st, void* post) {
   using namespace fa;
   auto al = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
   const int nw = (F1 + 63) / 64;
   char* const w0 = static_cast<char*>(ws);
   char* w = w0 + ws_used;
-  const int LM = std::min(max_levels, 31);
+  const int LM = std::min(max_levels, kDlMaxLevels);
   const int64_t acc_max = (int64_t)(lds / accb);
   int64_t nb = n1_bound;
-  int m = (int)desc[4] + 1;
-  const int32_t* P = reinterpret_cast<const int32_t*>((intptr_t)desc[3]);
+  int m = (int)desc[0].m + 1;
+  const int32_t* P = reinterpret_cast<const int32_t*>((intptr_t)desc[0].rows);
   struct Lv { int32_t* cnt; int64_t* off; int32_t* rows; int m; };
-  Lv lv[32];
+  Lv lv[kDlMaxL];
   // two pinned mirrors of the control block and their events (allocated once)
   static long long* mirror = nullptr;
   static hipEvent_t ev[2];
@@ -1265,28 +1217,26 @@ FA_API int fa_hip_dl_more(int F1, void* ws, int64_t ws_bytes, int64_t ws_used, l
   for (int q = 0; q < 2 && next < LM && rc == 0; ++q, next += kAgdBatch) rc = enqueue(next);
   for (int waited = 0; rc == 0 && waited < nbatch; ++waited) {
     if (hipEventSynchronize(ev[waited & 1]) != hipSuccess) return 7;
-    if (mirror[(waited & 1) * kDlCtl]) break;                     // the chain stopped
+    if (mirror[(waited & 1) * kDlCtl + kDlStop]) break;                     // the chain stopped
     if (next < LM) { rc = enqueue(next); next += kAgdBatch; }     // keep one batch ahead
   }
   (void)hipMemcpyAsync(ctl_host, ctl, sizeof(long long) * kDlCtl, hipMemcpyDeviceToHost, st);
   if (hipStreamSynchronize(st) != hipSuccess) return 7;
   if (rc) return rc;
-  desc[5] = ctl_host[8];
-  desc[6] = ctl_host[40];
-  desc[7] = 0;
-  const int L = (int)ctl_host[1];
-  int64_t base = desc[6];
+  desc[0].n = ctl_host[kDlNl];
+  desc[0].C = ctl_host[kDlCl];
+  desc[0].base = 0;
+  const int L = (int)ctl_host[kDlLevels];
   for (int l = 1; l < L; ++l) {
-    int64_t* d = desc + 8 * l;
-    d[0] = desc[8 * (l - 1) + 3];
-    d[1] = (int64_t)(intptr_t)lv[l].cnt;
-    d[2] = (int64_t)(intptr_t)lv[l].off;
-    d[3] = (int64_t)(intptr_t)lv[l].rows;
-    d[4] = lv[l].m;
-    d[5] = ctl_host[8 + l];
-    d[6] = ctl_host[40 + l];
-    d[7] = base;
-    base += d[6];
+    DlDesc& d = desc[l];
+    d.P = desc[l - 1].rows;
+    d.cnt = (int64_t)(intptr_t)lv[l].cnt;
+    d.off = (int64_t)(intptr_t)lv[l].off;
+    d.rows = (int64_t)(intptr_t)lv[l].rows;
+    d.m = lv[l].m;
+    d.n = ctl_host[kDlNl + l];
+    d.C = ctl_host[kDlCl + l];
+    d.base = desc[l - 1].base + desc[l - 1].C;
   }
   info[0] = w - w0;
   if (post) dl_post(static_cast<DlPost*>(post), desc, L, ctl, ctl_host, F1, st);

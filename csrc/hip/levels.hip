@@ -17,20 +17,14 @@
 //   b = {extension slab rows 0-7 (u16)},  c = {prefix slab rows 4-11 (u16)}
 // A parent row with c extensions gives c / 8 pieces of 8 and one of c % 8;
 // pieces are bucketed by n_ext, 8 first (the lanes of a wave then loop equally
-// long, as plan.cpp's counting sort).  Prefixes of up to 12 items ride in the
+// long, as plan.cpp's counting sort).  Prefixes of up to kDlInline (12) items ride in the
 // record; longer ones (up to kDlMaxM) are written to gpre, the record pointing there.
 #include "fa_hip.h"
+#include "../host/fa_dl.h"
 
 namespace fa {
 
-constexpr int kDlMaxL = 32;
-constexpr int kDlInline = 12;  // prefix ids inline in a piece record
-constexpr int kDlMaxM = 40;    // longest prefix a device bundle takes (ops.primitives.DL_MAX_M)
-constexpr int kDlCtlN = 1024;  // gen.hip kDlCtl
-constexpr int kDlBitsN = 512;  // gen.hip kDlBits: first word of the used-item bitset
-// ctl words used here: 512 .. 1023 used-item bitset (gen.hip), 220 pieces, 221 pieces
-// as int32 (the count kernel's G)
-
+// (the control block ctl, the level table desc and the limits kDl*: fa_dl.h)
 struct DlLevels {
   const int32_t* P[kDlMaxL];      // parent rows [n_l][m_l]
   const int32_t* cnt[kDlMaxL];    // extensions per parent row; their ids at cnt + n_l
@@ -55,7 +49,7 @@ __device__ __forceinline__ int dl_level_of(const DlLevels& D, int64_t t) {
 
 // rank -> slab row from the used-item bitset (one wave; lane l owns words 8l .. 8l+7)
 __global__ __launch_bounds__(64) void k_dl_map(const uint64_t* __restrict__ mk, int F1, int32_t* __restrict__ item_map) {
-  __shared__ int pre[512];
+  __shared__ int pre[kDlBitsW];
   const int lane = threadIdx.x;
   const int nwd = (F1 + 63) >> 6;
   int cnt8[8], tot = 0;
@@ -127,7 +121,7 @@ __global__ __launch_bounds__(kDlPB) void k_dl_pieces_count(const DlLevels D, int
 }
 
 // part -> exclusive slot base per (block, bucket), buckets 8, 7, .., 1 in that order;
-// the piece count into ctl[220] (int32 copy at ctl + 221, the count kernel's G)
+// the piece count into ctl[kDlPieces] (int32 copy at ctl + kDlPiecesI32, the count kernel's G)
 __global__ __launch_bounds__(1024) void k_dl_pieces_scan(int32_t* __restrict__ part, int64_t nblk,
                                                          long long* __restrict__ c) {
   __shared__ int wsum[16];
@@ -151,15 +145,15 @@ __global__ __launch_bounds__(1024) void k_dl_pieces_scan(int32_t* __restrict__ p
     }
   }
   if (threadIdx.x == 0) {
-    c[220] = carry;
-    reinterpret_cast<int32_t*>(c + 221)[0] = (int32_t)carry;
+    c[kDlPieces] = carry;
+    reinterpret_cast<int32_t*>(c + kDlPiecesI32)[0] = (int32_t)carry;
   }
 }
 
 __device__ __forceinline__ uint32_t dl_pk(int x, int y) { return (uint32_t)(x & 0xFFFF) | ((uint32_t)(y & 0xFFFF) << 16); }
 
 __device__ __forceinline__ void dl_write_rec(int4* __restrict__ rec, int64_t p, int64_t cand, int n_ext, int m,
-                                             const int (&ids)[12], const int32_t* __restrict__ ex,
+                                             const int (&ids)[kDlInline], const int32_t* __restrict__ ex,
                                              const int32_t* __restrict__ item_map, int64_t goff) {
   int e8[8];
 #pragma unroll
@@ -208,9 +202,9 @@ __global__ __launch_bounds__(kDlPB) void k_dl_pieces_emit(const DlLevels D, cons
   const int64_t i = t - D.rbase[l];
   const int m = D.m[l];
   const int32_t* x = D.P[l] + i * m;
-  int ids[12];
+  int ids[kDlInline];
 #pragma unroll
-  for (int q = 0; q < 12; ++q) ids[q] = q < m ? item_map[x[q]] : 0;
+  for (int q = 0; q < kDlInline; ++q) ids[q] = q < m ? item_map[x[q]] : 0;
   int64_t goff = -1;
   if (m > kDlInline) {
     goff = D.gbase[l] + i * m;
@@ -249,7 +243,7 @@ __global__ __launch_bounds__(kDlPB) void k_dl_pieces_emit(const DlLevels D, cons
 // the deal's sequential latency grows with the window).
 // ---------------------------------------------------------------------------
 constexpr int kLaWs = 4;             // wave steps per window: 16 lane groups (one DPP row)
-constexpr int kLaMaxPos = 20;        // 12 inline prefix rows + 8 extensions
+constexpr int kLaMaxPos = kDlInline + 8;   // inline prefix rows + 8 extensions
 
 __device__ __forceinline__ int la_u16(const int4& v, int k) {
   const int w = (k >> 1) == 0 ? v.x : (k >> 1) == 1 ? v.y : (k >> 1) == 2 ? v.z : v.w;
@@ -301,7 +295,7 @@ __global__ __launch_bounds__(64) void k_dl_lane_assign(int4* __restrict__ rec, c
   __shared__ uint32_t st[kLaMaxPos][16][NG];       // [position][slot][group]: a read of one slot by the
                                                   // 16 groups hits 16 banks (group-major: one bank)
   __shared__ int16_t dst[NW];
-  const int G = reinterpret_cast<const int32_t*>(c + 221)[0];
+  const int G = reinterpret_cast<const int32_t*>(c + kDlPiecesI32)[0];
   const int64_t base = (int64_t)blockIdx.x * NW;
   if (base + NW > G) return;                       // a partial last window keeps its order
   const int lane = threadIdx.x;
@@ -313,7 +307,7 @@ __global__ __launch_bounds__(64) void k_dl_lane_assign(int4* __restrict__ rec, c
   for (int i = lane; i < NW; i += 64) same = same && (win[3 * i].y & 0x1FFFF) == y0;
   if (__ballot(!same) != 0ull) return;             // mixed n_ext / m (bucket or level edge)
   const int n_ext = y0 & 0xFF, m = (y0 >> 8) & 0xFF;
-  if ((y0 >> 16) || m > 12 || m + n_ext > kLaMaxPos) return;
+  if ((y0 >> 16) || m > kDlInline || m + n_ext > kLaMaxPos) return;
   const int R = m + n_ext;
   for (int i = lane; i < NW; i += 64) {
     const int4 a = win[3 * i], b = win[3 * i + 1], cc = win[3 * i + 2];
@@ -544,7 +538,7 @@ __global__ __launch_bounds__(256) void k_dlt_emit(const DlLevels D, const DlOut 
 
 // levels of a bundle from gen.hip's level table; gpre / gpre_cap: room for the prefix
 // slab rows of levels whose prefixes exceed kDlInline ids (returns 1 when too small)
-static int dl_levels(const int64_t* desc, int L, DlLevels* D, int32_t* gpre = nullptr, int64_t gpre_cap = 0) {
+static int dl_levels(const DlDesc* desc, int L, DlLevels* D, int32_t* gpre = nullptr, int64_t gpre_cap = 0) {
   if (L < 1 || L > kDlMaxL) return 1;
   *D = DlLevels{};
   D->L = L;
@@ -554,21 +548,21 @@ static int dl_levels(const int64_t* desc, int L, DlLevels* D, int32_t* gpre = nu
   D->gpre = gpre;
   int64_t g = 0;
   for (int l = 0; l < L; ++l) {
-    const int64_t* d = desc + 8 * l;
-    D->P[l] = reinterpret_cast<const int32_t*>((intptr_t)d[0]);
-    D->cnt[l] = reinterpret_cast<const int32_t*>((intptr_t)d[1]);
-    D->off[l] = reinterpret_cast<const int64_t*>((intptr_t)d[2]);
-    D->rows[l] = reinterpret_cast<const int32_t*>((intptr_t)d[3]);
-    D->m[l] = (int)d[4];
-    D->n[l] = d[5];
-    D->C[l] = d[6];
-    D->base[l] = d[7];
-    D->rbase[l + 1] = D->rbase[l] + d[5];
+    const DlDesc& d = desc[l];
+    D->P[l] = reinterpret_cast<const int32_t*>((intptr_t)d.P);
+    D->cnt[l] = reinterpret_cast<const int32_t*>((intptr_t)d.cnt);
+    D->off[l] = reinterpret_cast<const int64_t*>((intptr_t)d.off);
+    D->rows[l] = reinterpret_cast<const int32_t*>((intptr_t)d.rows);
+    D->m[l] = (int)d.m;
+    D->n[l] = d.n;
+    D->C[l] = d.C;
+    D->base[l] = d.base;
+    D->rbase[l + 1] = D->rbase[l] + d.n;
     if (D->m[l] < 1 || D->m[l] > kDlMaxM) return 1;
     D->gbase[l] = -1;
     if (D->m[l] > kDlInline) {
       D->gbase[l] = g;
-      g += d[5] * D->m[l];
+      g += d.n * D->m[l];
     }
   }
   if (g > 0 && gpre_cap >= 0 && (gpre == nullptr || g > gpre_cap)) return 1;   // (cap < 0: not planning)
@@ -579,10 +573,10 @@ static int dl_levels(const int64_t* desc, int L, DlLevels* D, int32_t* gpre = nu
 
 using namespace fa;
 
-FA_API int fa_hip_dl_plan_window(const int64_t* desc, int L, long long* ctl, int F1, int32_t* item_map, void* rec,
+FA_API int fa_hip_dl_plan_window(const DlDesc* desc, int L, long long* ctl, int F1, int32_t* item_map, void* rec,
                                  int64_t max_pieces, int32_t* part, int64_t part_cap, int32_t* gpre,
                                  int64_t gpre_cap, int64_t w0, int64_t w1, int sw, hipStream_t st);
-FA_API int fa_hip_dl_plan_window_bits(const int64_t* desc, int L, long long* ctl, int F1, const uint64_t* used_bits,
+FA_API int fa_hip_dl_plan_window_bits(const DlDesc* desc, int L, long long* ctl, int F1, const uint64_t* used_bits,
                                       int32_t* item_map, void* rec, int64_t max_pieces, int32_t* part,
                                       int64_t part_cap, int32_t* gpre, int64_t gpre_cap, int64_t w0, int64_t w1,
                                       int sw, hipStream_t st);
@@ -602,8 +596,8 @@ FA_API void fa_hip_set_lane_deal(int on) { g_lane_on = on; }
 // rec: int4 [3 * max_pieces] out, max_pieces >= total candidates; part: int32
 // scratch of 8 per 256 parent rows (part_cap); gpre: int32 [gpre_cap] out, the prefix
 // slab rows of levels with prefixes past kDlInline ids (fa_hip_dl_gpre_need).  The
-// piece count lands in ctl[220] (int32 copy at ctl + 221, the count kernel's G).
-FA_API int fa_hip_dl_plan(const int64_t* desc, int L, long long* ctl, int F1, int32_t* item_map, void* rec,
+// piece count lands in ctl[kDlPieces] (int32 copy at ctl + kDlPiecesI32, the count kernel's G).
+FA_API int fa_hip_dl_plan(const DlDesc* desc, int L, long long* ctl, int F1, int32_t* item_map, void* rec,
                           int64_t max_pieces, int32_t* part, int64_t part_cap, int32_t* gpre, int64_t gpre_cap,
                           int sw, hipStream_t st) {
   return fa_hip_dl_plan_window(desc, L, ctl, F1, item_map, rec, max_pieces, part, part_cap, gpre, gpre_cap, 0, -1, sw,
@@ -612,7 +606,7 @@ FA_API int fa_hip_dl_plan(const int64_t* desc, int L, long long* ctl, int F1, in
 
 // The plan of the bundle candidates [w0, w1) only (w1 < 0: all): one pass of a level
 // whose candidates exceed one accumulator pass; records index candidates from w0.
-FA_API int fa_hip_dl_plan_window(const int64_t* desc, int L, long long* ctl, int F1, int32_t* item_map, void* rec,
+FA_API int fa_hip_dl_plan_window(const DlDesc* desc, int L, long long* ctl, int F1, int32_t* item_map, void* rec,
                                  int64_t max_pieces, int32_t* part, int64_t part_cap, int32_t* gpre,
                                  int64_t gpre_cap, int64_t w0, int64_t w1, int sw, hipStream_t st) {
   return fa_hip_dl_plan_window_bits(desc, L, ctl, F1, nullptr, item_map, rec, max_pieces, part, part_cap, gpre,
@@ -622,13 +616,13 @@ FA_API int fa_hip_dl_plan_window(const int64_t* desc, int L, long long* ctl, int
 // ... with the window's own used items (used_bits: device bitset of F1 bits, e.g. the OR
 // of fa_hip_dl_chunk_bits' chunks of the window; nullptr: the level's, ctl's bitset):
 // the slab rows of the window are only the items its candidates use
-FA_API int fa_hip_dl_plan_window_bits(const int64_t* desc, int L, long long* ctl, int F1, const uint64_t* used_bits,
+FA_API int fa_hip_dl_plan_window_bits(const DlDesc* desc, int L, long long* ctl, int F1, const uint64_t* used_bits,
                                       int32_t* item_map, void* rec, int64_t max_pieces, int32_t* part,
                                       int64_t part_cap, int32_t* gpre, int64_t gpre_cap, int64_t w0, int64_t w1,
                                       int sw, hipStream_t st) {
   DlLevels D;
   if (dl_levels(desc, L, &D, gpre, gpre_cap)) return 1;
-  if (F1 < 1 || F1 > 32768) return 1;
+  if (F1 < 1 || F1 > kAgMaxF1) return 1;
   int64_t C = 0;
   for (int l = 0; l < L; ++l) C += D.C[l];
   D.w0 = w0 < 0 ? 0 : w0;
@@ -638,7 +632,7 @@ FA_API int fa_hip_dl_plan_window_bits(const int64_t* desc, int L, long long* ctl
   const int64_t R = D.rbase[L];
   const int64_t nblk = std::max<int64_t>(1, (R + kDlPB - 1) / kDlPB);
   if (part_cap < 8 * nblk) return 1;
-  const uint64_t* mk = used_bits ? used_bits : reinterpret_cast<const uint64_t*>(ctl + kDlBitsN);
+  const uint64_t* mk = used_bits ? used_bits : reinterpret_cast<const uint64_t*>(ctl + kDlBits);
   hipLaunchKernelGGL(k_dl_map, dim3(1), dim3(64), 0, st, mk, F1, item_map);
   hipLaunchKernelGGL(k_dl_pieces_count, dim3((unsigned)nblk), dim3(kDlPB), 0, st, D, part);
   hipLaunchKernelGGL(k_dl_pieces_scan, dim3(1), dim3(1024), 0, st, part, nblk, ctl);
@@ -655,12 +649,12 @@ FA_API int fa_hip_dl_plan_window_bits(const int64_t* desc, int L, long long* ctl
 
 // Used-item bitset of every chunk of `chunk` candidates of a single-level plan's
 // candidate rows (desc level 0: rows [C][m + 1]): out[j * nwd .. (j + 1) * nwd) for
-// chunk j (nwd = ceil(F1 / 64) <= 512).  The window planner of a multi-pass level
+// chunk j (nwd = ceil(F1 / 64) <= kDlBitsW).  The window planner of a multi-pass level
 // (ops.primitives.dl_count_multipass) grows each window chunk by chunk while its
 // candidates fit the accumulators left by its own used items' slab rows.
 __global__ __launch_bounds__(256) void k_dl_chunk_bits(const int32_t* __restrict__ rows, int64_t C, int w, int chunk,
                                                        int nwd, unsigned long long* __restrict__ out) {
-  __shared__ unsigned long long lb[512];
+  __shared__ unsigned long long lb[kDlBitsW];
   for (int i = threadIdx.x; i < nwd; i += 256) lb[i] = 0ull;
   __syncthreads();
   const int64_t c0 = (int64_t)blockIdx.x * chunk, c1 = min(C, c0 + chunk);
@@ -672,13 +666,13 @@ __global__ __launch_bounds__(256) void k_dl_chunk_bits(const int32_t* __restrict
   for (int i = threadIdx.x; i < nwd; i += 256) out[(int64_t)blockIdx.x * nwd + i] = lb[i];
 }
 
-FA_API int fa_hip_dl_chunk_bits(const int64_t* desc, int F1, int chunk, uint64_t* out, hipStream_t st) {
+FA_API int fa_hip_dl_chunk_bits(const DlDesc* desc, int F1, int chunk, uint64_t* out, hipStream_t st) {
   const int nwd = (F1 + 63) / 64;
-  const int64_t C = desc[6];
-  if (F1 < 1 || nwd > 512 || chunk < 1 || C < 1) return 1;
-  const int32_t* rows = reinterpret_cast<const int32_t*>((intptr_t)desc[3]);
+  const int64_t C = desc[0].C;
+  if (F1 < 1 || nwd > kDlBitsW || chunk < 1 || C < 1) return 1;
+  const int32_t* rows = reinterpret_cast<const int32_t*>((intptr_t)desc[0].rows);
   const int64_t nch = (C + chunk - 1) / chunk;
-  hipLaunchKernelGGL(k_dl_chunk_bits, dim3((unsigned)nch), dim3(256), 0, st, rows, C, (int)desc[4] + 1, chunk, nwd,
+  hipLaunchKernelGGL(k_dl_chunk_bits, dim3((unsigned)nch), dim3(256), 0, st, rows, C, (int)desc[0].m + 1, chunk, nwd,
                      reinterpret_cast<unsigned long long*>(out));
   FA_LAUNCH_RET();
 }
@@ -688,7 +682,7 @@ FA_API int fa_hip_dl_chunk_bits(const int64_t* desc, int F1, int chunk, uint64_t
 // (int32 [F]); F of level l into fsz[l] (device).  rows_off / cnt_off: host int64 [L].
 // scratch (optional): int32 [scratch_cap] for the multi-workgroup form (bundles of more
 // than 4096 candidates; one per kThB candidates of each level, fa_hip_dl_threshold_scratch).
-FA_API int fa_hip_dl_threshold(const int64_t* desc, int L, const uint32_t* counts, int64_t mc, int32_t* rows_out,
+FA_API int fa_hip_dl_threshold(const DlDesc* desc, int L, const uint32_t* counts, int64_t mc, int32_t* rows_out,
                                const int64_t* rows_off, int32_t* cnt_out, const int64_t* cnt_off, long long* fsz,
                                int32_t* scratch, int64_t scratch_cap, hipStream_t st) {
   DlLevels D;
@@ -713,16 +707,16 @@ FA_API int fa_hip_dl_threshold(const int64_t* desc, int L, const uint32_t* count
   FA_LAUNCH_RET();
 }
 
-FA_API int64_t fa_hip_dl_threshold_scratch(const int64_t* desc, int L) {
+FA_API int64_t fa_hip_dl_threshold_scratch(const DlDesc* desc, int L) {
   int64_t n = 0;
-  for (int l = 0; l < L; ++l) n += (desc[8 * l + 6] + kThB - 1) / kThB;
+  for (int l = 0; l < L; ++l) n += (desc[l].C + kThB - 1) / kThB;
   return n;
 }
 
 // int32 entries of gpre a bundle needs (levels with prefixes past kDlInline ids)
-FA_API int64_t fa_hip_dl_gpre_need(const int64_t* desc, int L) {
+FA_API int64_t fa_hip_dl_gpre_need(const DlDesc* desc, int L) {
   int64_t g = 0;
   for (int l = 0; l < L; ++l)
-    if (desc[8 * l + 4] > kDlInline) g += desc[8 * l + 5] * desc[8 * l + 4];
+    if (desc[l].m > kDlInline) g += desc[l].n * desc[l].m;
   return g;
 }

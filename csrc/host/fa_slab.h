@@ -32,7 +32,10 @@
 //     map (fa_hip_count_slab_rec_cls).  dl_post and dl_count do the same;
 //     dl_count_multipass rounds but omits the map; count_level includes the map but
 //     charges the unrounded accumulators (the same count whenever the budget is a
-//     multiple of 32 B, as the default is).
+//     multiple of 32 B, as the default is).  (The launch's mode bits, and the rest of
+//     what dl_post and dl_count share with the kernels -- control block, level
+//     table, DlPost -- are fa_dl.h's; Python assembles the launch once, in
+//     ops.primitives._slab_count, with each caller's charge.)
 #pragma once
 #include <math.h>
 #include <stdint.h>

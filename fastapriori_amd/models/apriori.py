@@ -345,7 +345,7 @@ class FastApriori:
     # ------------------------------------------------------------------
     def _device_levels_planned(self, resume) -> bool:
         return (TUNING.device_levels and self._dev.type == "cuda"
-                and 2 <= self._F1 <= ops.primitives.DL_MAX_F1
+                and 2 <= self._F1 <= ops.primitives.dl().kAgMaxF1
                 and self.cfg.level_kernel in ("auto", "slab") and self.stats["n_lines"] < (1 << 31)
                 and (self.cfg.max_level == 0 or self.cfg.max_level >= 3))
 
@@ -391,6 +391,7 @@ class FastApriori:
         continues (a level that needs several accumulator passes, or prefixes too long
         for inline piece records): levels/counts then hold F_1 .. F_{k-1}."""
         Pm = ops.primitives
+        K = Pm.dl()                       # the control block's slots and the loop's limits (csrc/host/fa_dl.h)
         S = Pm.device_level_state(self._dev)
         F1 = self._F1
         lds = Pm.dl_lds_budget(F1)
@@ -425,13 +426,13 @@ class FastApriori:
         while True:
             if self.cfg.max_level and k > self.cfg.max_level:
                 break
-            if m0 > Pm.DL_MAX_M:
+            if m0 > K.kDlMaxM:
                 nxt = k
                 break
             t0 = time.perf_counter()
             b0 = self._bytes_moved()
             with roctx_range(f"dlevel{k}"), tm.phase(f"level{k}"):
-                max_lv = min(Pm.DL_MAX_M - m0 + 1, Pm.DL_MAX_LEVELS)
+                max_lv = min(K.kDlMaxM - m0 + 1, K.kDlMaxLevels)
                 if self.cfg.max_level:
                     max_lv = min(max_lv, self.cfg.max_level - k + 1)
                 if not TUNING.bundle_levels or k - 1 > TUNING.bundle_max_prefix:
@@ -447,12 +448,12 @@ class FastApriori:
                 with roctx_range("gen"):
                     c = Pm.dl_bundle_gen(S, P0, n_src, n_const, n_bound, m0, F1, c_bound, lds, TUNING.bundle_growth,
                                          max_lv, st, post=post, accb=accb)
-                if c[4]:
+                if c[K.kDlOverBound]:
                     raise RuntimeError(f"device bundle at level {k}: |F_{k - 1}| exceeds its bound {n_bound}")
-                if c[7]:
+                if c[K.kDlEnd]:
                     break                               # |F_{k-1}| < k or no candidates: done
                 multi = None
-                if c[5]:
+                if c[K.kDlMulti]:
                     # level k alone needs several accumulator passes: counted on the device
                     # window by window (else the host loop takes over from level k)
                     multi = self._dl_multipass(S, db, k, F1, c, P0, n_src, n_const, n_bound, m0, lds, st)
@@ -460,8 +461,8 @@ class FastApriori:
                         nxt = k
                         break
                     c = multi[0]
-                L, n_used = int(c[1]), int(c[6])
-                Cs = S.desc[:L, 6].copy()
+                L, n_used = int(c[K.kDlLevels]), int(c[K.kDlNUsed])
+                Cs = S.desc["C"][:L].copy()
                 C = int(Cs.sum())
                 done = int(S.post.done) if post else 0
                 sw = int(S.post.sw) if done else 0
@@ -473,7 +474,7 @@ class FastApriori:
                     cnt = S.post_bufs["out"][:C]
                 else:
                     nwd = (F1 + 63) // 64
-                    bits = np.unpackbits(c[Pm.DL_BITS:Pm.DL_BITS + nwd].view(np.uint8), bitorder="little")[:F1]
+                    bits = np.unpackbits(c[K.kDlBits:K.kDlBits + nwd].view(np.uint8), bitorder="little")[:F1]
                     used = np.flatnonzero(bits)
                     if done == 1:
                         plan = Pm.dl_plan_from_post(S, n_used)
@@ -496,9 +497,9 @@ class FastApriori:
             hbm_rows = (db["ranks"].numel() * db["ranks"].element_size()
                         + db["roff"].numel() * db["roff"].element_size())
             pend.append(dict(k=k, L=L, m0=m0, C=Cs, rows=rows_a, cnt=cnt_a, ro=ro, co=co, hbm_rows=int(hbm_rows),
-                             n_par=S.desc[:L, 5].copy(), sw=sw, used=n_used, T=int(db["roff"].numel() - 1),
+                             n_par=S.desc["n"][:L].copy(), sw=sw, used=n_used, T=int(db["roff"].numel() - 1),
                              ms=(time.perf_counter() - t0) * 1e3, bytes=self._bytes_moved() - b0,
-                             G=c[72:72 + L].copy(), nz=nz))
+                             G=c[K.kDlGl:K.kDlGl + L].copy(), nz=nz))
             P0 = rows_a.data_ptr() + 4 * int(ro[L - 1])
             n_src, n_const, n_bound = S.fsz.data_ptr() + 8 * (k + L - 1), 0, int(Cs[-1])
             m0 += L
@@ -507,7 +508,7 @@ class FastApriori:
             # trip): |F_{k-1}| <= C_{k-1} < k fails the reference's loop test
             # (FastApriori.scala:111), or the chain already found no k-candidates from
             # C_{k-1}, a superset of F_{k-1}
-            if int(Cs[-1]) < k or (multi is None and int(c[Pm.DL_EMPTY])):
+            if int(Cs[-1]) < k or (multi is None and int(c[K.kDlEmpty])):
                 break
         self._dl_flush(S, pend, levels, counts, result)
         if self.cand_par and pend:
@@ -528,17 +529,18 @@ class FastApriori:
         not even 4-word slabs of the used items fit the LDS (wide levels: thousands of
         used items), the level is counted by the bitmap kernel instead (_dl_bitmap_count)."""
         Pm = ops.primitives
+        K = Pm.dl()
         if not TUNING.dl_multi or self.cfg.max_level and k > self.cfg.max_level:
             return None
-        C0 = int(c[40])
-        if int(c[1]) == 0:
+        C0 = int(c[K.kDlCl])
+        if int(c[K.kDlLevels]) == 0:
             # the bounded generation reported the size only: again, one level, room for C0
             c = Pm.dl_bundle_gen(S, P0, n_src, n_const, n_bound, m0, F1, C0, lds, TUNING.bundle_growth, 1, st,
                                  accb=self._dl_accb)
-            if c[4] or c[7] or int(c[1]) != 1 or int(c[40]) != C0:
+            if c[K.kDlOverBound] or c[K.kDlEnd] or int(c[K.kDlLevels]) != 1 or int(c[K.kDlCl]) != C0:
                 raise RuntimeError(f"device level {k}: regeneration of {C0} candidates disagrees ({c[:8]})")
         nwd = (F1 + 63) // 64
-        bits = np.unpackbits(c[Pm.DL_BITS:Pm.DL_BITS + nwd].view(np.uint8), bitorder="little")[:F1]
+        bits = np.unpackbits(c[K.kDlBits:K.kDlBits + nwd].view(np.uint8), bitorder="little")[:F1]
         used = np.flatnonzero(bits)
         n_used = int(used.size)
         wide = Pm.slab_width(n_used, C0, lds, self._dl_mp_accb)[0] == 0
@@ -634,8 +636,9 @@ class FastApriori:
         are read where the generator wrote them (its workspace), grouped by prefix on
         the device; one readback of the group offsets."""
         Pm = ops.primitives
-        m, C = int(S.desc[0, 4]), int(S.desc[0, 6])
-        off = int(S.desc[0, 3]) - S.ws.data_ptr()
+        d0 = S.desc[0]
+        m, C = int(d0["m"]), int(d0["C"])
+        off = int(d0["rows"]) - S.ws.data_ptr()
         if off < 0 or off % 4 or off + 4 * C * (m + 1) > S.ws.numel():
             raise RuntimeError("device bundle: candidate rows outside the generator workspace")
         rows = S.ws[off:off + 4 * C * (m + 1)].view(torch.int32).view(C, m + 1)
@@ -689,9 +692,10 @@ class FastApriori:
         current rows and the trimming inputs of level k (FastApriori._trim_worth_it)."""
         Pm = ops.primitives
         m0 = k - 1
-        # prefixes past 12 ids ride in gpre (levels.hip); a bundle needing more than this
-        # room is planned by dl_plan with the exact size instead
-        gpre_n = n_bound * m0 if m0 > 12 else (c_bound * (m0 + 4) if m0 + Pm.DL_MAX_LEVELS > 12 else 0)
+        # prefixes past kDlInline ids ride in gpre (levels.hip); a bundle needing more than
+        # this room is planned by dl_plan with the exact size instead
+        K = Pm.dl()
+        gpre_n = n_bound * m0 if m0 > K.kDlInline else (c_bound * (m0 + 4) if m0 + K.kDlMaxLevels > K.kDlInline else 0)
         b = S.post_buffers(F1, c_bound, n_bound + c_bound, min(gpre_n, 1 << 24))
         P = S.post
         P.item_map, P.rec, P.part, P.out = (b["item_map"].data_ptr(), b["rec"].data_ptr(), b["part"].data_ptr(),
@@ -1495,11 +1499,11 @@ class FastApriori:
         dev = self._dev
         n = prev.shape[0]
         if (dev.type == "cuda" and TUNING.gen_device and n >= TUNING.gen_device_min_rows and prev.shape[1] >= 2
-                and self._F1 <= ops.primitives.AG_DEVICE_MAX_F1):
+                and self._F1 <= ops.primitives.dl().kAgMaxF1):
             return ops.apriori_gen_device(prev, self._F1, dev, want_rows)
-        if dev.type == "cuda" and self._F1 > ops.primitives.AG_DEVICE_MAX_F1:
+        if dev.type == "cuda" and self._F1 > ops.primitives.dl().kAgMaxF1:
             ops.primitives.note_fallback(f"apriori-gen on the host: F1 = {self._F1} frequent items exceed the "
-                                         f"device generator's {ops.primitives.AG_DEVICE_MAX_F1}-rank bitsets")
+                                         f"device generator's {ops.primitives.dl().kAgMaxF1}-rank bitsets")
         pi, eo, ex = apriori_gen(prev)
         if not want_rows:
             return pi, eo, ex
@@ -1516,7 +1520,7 @@ class FastApriori:
         if not (dev.type == "cuda" and TUNING.gen_device and TUNING.gen_chain and TUNING.bundle_levels
                 and self.cfg.level_kernel in ("auto", "slab") and k - 1 <= TUNING.bundle_max_prefix
                 and prev.shape[0] >= TUNING.gen_device_min_rows and prev.shape[1] >= 2
-                and self._F1 <= ops.primitives.AG_DEVICE_MAX_F1):
+                and self._F1 <= ops.primitives.dl().kAgMaxF1):
             return None
         max_lv = (self.cfg.max_level - k + 1) if self.cfg.max_level else 64
         with roctx_range("gen_bundle"), self._timer.phase("apriori_gen"):
@@ -1565,7 +1569,7 @@ class FastApriori:
         kk = k
         dev = self._dev
         if (dev.type == "cuda" and TUNING.gen_device and TUNING.gen_chain and cand.shape[1] >= 2
-                and self._F1 <= ops.primitives.AG_DEVICE_MAX_F1):
+                and self._F1 <= ops.primitives.dl().kAgMaxF1):
             # all speculative levels in one native call (one 8-byte readback per level)
             max_lv = (self.cfg.max_level - k) if self.cfg.max_level else 64
             tmax = ops.primitives.slab_total_limit(n_used, TUNING.slab_lds_bytes)

@@ -48,6 +48,8 @@ _HOST_SIGS = {
     "fa_slab_map_lds": (i64, [i64]),
     "fa_slab_workgroups": (i64, [i64, i64, C.c_int, i64, C.c_int, i64, i64]),
     "fa_trim_estimate": (None, [vp, i64, dbl, C.c_int, C.POINTER(dbl), C.POINTER(dbl)]),
+    # the device bundle loop's slots, limits, mode bits and struct layouts by name (csrc/host/fa_dl.h)
+    "fa_dl_layout": (cp, [C.c_int, I64P]),
     "fa_f1_rank_numeric": (i64, [vp, i64, i64, vp, vp, vp]),
     "fa_rules_build": (vp, [vp, vp, vp, C.c_int, vp, C.c_int, vp]),
     "fa_rules_nante": (i64, [vp]),
@@ -94,8 +96,6 @@ _HIP_SIGS = {
     "fa_hip_block_bsum": (C.c_int, [vp, i64, i64, C.c_int, vp, vp]),
     "fa_hip_compress_staged": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp]),
     "fa_hip_compress_staged64": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, C.c_int, vp]),
-    "fa_hip_count_slab_rec": (C.c_int, [vp, vp, vp, i64, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp,
-                                        C.c_int, C.c_int, vp, i64, vp, vp, vp]),
     "fa_hip_count_slab_rec_cls": (C.c_int, [vp, vp, vp, i64, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp,
                                             vp, C.c_int, C.c_int, vp, i64, vp, vp, vp, C.c_int]),
     # device-resident level bundles (gen.hip fa_hip_dl_*, levels.hip)

@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import ctypes
+import functools
 import os
 import time
 from dataclasses import dataclass
@@ -870,6 +871,31 @@ def _slab_workgroups(nslabs: int, n_used: int, sw: int, n_acc: int, round_acc: b
                                                  int(map_bytes), int(TUNING.slab_lds_bytes)))
 
 
+def _slab_dense(wword, sw: int, sup_frac: float) -> bool:
+    """count_level's dense test: the slab kernel drops its all-zero-prefix test (sup_frac 0: never)."""
+    return wword is None and TUNING.dense_min_rows > 0 and sup_frac * sw * 64 >= TUNING.dense_min_rows
+
+
+def _slab_count(*, roff, ranks, src, ncols: int, item_map, F1: int, n_used: int, gpre, rec, C: int, wword, out,
+                sw: int, st: int, round_acc: bool, map_bytes: int, G: int = 0, g_dev=None, bm=None, bm_ld: int = 0,
+                bm_rows=None, cls: int = 0, accb: float = 4.0, sup_frac: float = 0.0) -> None:
+    """One slab count (count.hip fa_hip_count_slab_rec_cls) of C candidates over ncols
+    columns; roff .. out, g_dev, bm, bm_rows: device addresses or None.  The pieces are
+    rec's first G, or as many as the int32 at g_dev says (device plans: ctl's
+    kDlPiecesI32).  accb 2: packed u16 accumulators when the rows have unit weights;
+    cls: kSlabCls when rec carries class-layout flags; sup_frac: _slab_dense.
+    round_acc, map_bytes: what the caller charges a workgroup's LDS (_slab_workgroups;
+    csrc/host/fa_slab.h lists the callers' charges)."""
+    K = dl()
+    nslabs = ((ncols + 63) // 64 + sw - 1) // sw
+    acc16 = accb == 2 and wword is None
+    nacc = (C + 1) // 2 if acc16 else C
+    n_wg = _slab_workgroups(nslabs, n_used, sw, nacc, round_acc, map_bytes)
+    mode = cls | (K.kSlabDense if _slab_dense(wword, sw, sup_frac) else 0) | (K.kSlabAcc16 if acc16 else 0)
+    _hip_call("fa_hip_count_slab_rec_cls", roff, ranks, src, ncols, item_map, F1, n_used, gpre, rec, G, C, wword,
+              out, sw, n_wg, bm, bm_ld, st, bm_rows, g_dev, mode)
+
+
 # TUNING.slab_cls: class layout of slab passes (plan.cpp cls_layout, k_count_slab_rec<..,
 # kCls>): sibling prefixes share their first m-1 rows in registers; 0 disables it.
 # TUNING.dense_min_rows (count_level): expected rows per slab of the rarest frequent prefix
@@ -1048,27 +1074,21 @@ def count_level(roff, ranks, src, ncols: int, F1: int, prefix: np.ndarray, ext_o
                                   dbuf[o_used:o_used + n_used])
     st = _stream(ranks)
     bounds = passes[:, 2].tolist() + [C]
-    nslabs = (W + sw - 1) // sw
-    dense = wword is None and TUNING.dense_min_rows > 0 and sup_frac * sw * 64 >= TUNING.dense_min_rows
     map_b = slab_map_lds(F1)
     for q, (a, b, e0) in enumerate(passes.tolist()):
-        Cq = bounds[q + 1] - e0
         # piece records (k_count_slab_rec): 48 B per piece, loaded one piece ahead
-        n_wg = _slab_workgroups(nslabs, n_used, sw, Cq, False, map_b)
-        _hip_call("fa_hip_count_slab_rec_cls", _p(roff), _p(ranks), _p(src), ncols, base + 4 * o_im, F1,
-                  n_used, base + 4 * o_gpre, base + 4 * (o_rec + 12 * a), b - a, Cq, _p(wword),
-                  out.data_ptr() + 4 * e0, sw, n_wg, _p(bm), bitmap_ld(bm), st,
-                  bm_rows, None, int(info[23]) | (2 if dense else 0))
+        _slab_count(roff=_p(roff), ranks=_p(ranks), src=_p(src), ncols=ncols, item_map=base + 4 * o_im, F1=F1,
+                    n_used=n_used, gpre=base + 4 * o_gpre, rec=base + 4 * (o_rec + 12 * a), G=b - a,
+                    C=bounds[q + 1] - e0, wword=_p(wword), out=out.data_ptr() + 4 * e0, sw=sw, st=st,
+                    round_acc=False, map_bytes=map_b, bm=_p(bm), bm_ld=bitmap_ld(bm), bm_rows=bm_rows,
+                    cls=dl().kSlabCls if info[23] else 0, sup_frac=sup_frac)
     CLS_LEVELS[0] += int(info[23])
     LAST_LEVEL_PLAN.clear()
     LAST_LEVEL_PLAN.update(kernel="slab", rows=int(roff.numel() - 1), used=n_used, sw=sw,
                            cap=cap, passes=npass, pieces=int(info[4]), slab_reads=int(info[10]), m=m, C=C,
                            cls=int(info[23]), step_reads=int(info[21]), step_reads_cls=int(info[22]),
-                           dense=bool(dense))
+                           dense=bool(_slab_dense(wword, sw, sup_frac)))
     return out.to(_I64)
-
-
-AG_DEVICE_MAX_F1 = 32768  # device apriori-gen: up to 8 bitset words per lane of a 64-lane wave (gen.hip)
 
 
 def ag_mark_words(F1: int) -> int:
@@ -1537,16 +1557,41 @@ def parse_dict_device(buf: torch.Tensor, n: int, last_is_term: bool):
 # csrc/hip/levels.hip fa_hip_dl_plan / fa_hip_dl_threshold; driven by
 # models.apriori.FastApriori._mine_device)
 # ---------------------------------------------------------------------------
-DL_CTL = 1024           # gen.hip kDlCtl
-DL_BITS = 512           # gen.hip kDlBits: the control block's used-item bitset (ctl[512:1024])
-DL_EMPTY = 104          # gen.hip kDlEmpty: the chain stopped on a level without candidates
-DL_MAX_F1 = 32768       # its bits (and the generator's 8 bitset words per lane)
-DL_MAX_M = 40           # levels.hip kDlMaxM (prefixes past 12 ids go through gpre)
-DL_MAX_LEVELS = 31
+class _DlLayout:
+    """csrc/host/fa_dl.h by name, read from libfa_host.so (fa_dl_layout) at first use: the
+    control block's slots (kDlStop ..), the limits and the slab count's mode bits as
+    attributes under their C++ names; desc_dtype, the level table's record type (DlDesc);
+    post_size / post_offsets, DlPost's layout; table, every exported (name, value)."""
+
+    def __init__(self):
+        lib, v, i = _native.host(), ctypes.c_int64(0), 0
+        self.table = {}
+        while (name := lib.fa_dl_layout(i, ctypes.byref(v))) is not None:
+            self.table[name.decode()] = int(v.value)
+            i += 1
+        for name, val in self.table.items():
+            if name.isidentifier():
+                setattr(self, name, val)
+        desc = sorted((off, n[7:]) for n, off in self.table.items() if n.startswith("DlDesc."))
+        self.desc_dtype = np.dtype(dict(names=[n for _, n in desc], formats=[np.int64] * len(desc),
+                                        offsets=[off for off, _ in desc], itemsize=self.table["sizeof(DlDesc)"]))
+        self.post_size = self.table["sizeof(DlPost)"]
+        self.post_offsets = {n[7:]: off for n, off in self.table.items() if n.startswith("DlPost.")}
+
+
+class _DescTable(np.ndarray):
+    """Level table (desc_dtype records); a row also takes its values as a list in DlDesc's order."""
+    def __setitem__(self, key, value):
+        super().__setitem__(key, tuple(value) if isinstance(value, list) else value)
+
+
+@functools.lru_cache(maxsize=None)
+def dl() -> _DlLayout:
+    return _DlLayout()
 
 
 class DlPostC(ctypes.Structure):
-    """gen.hip DlPost: what fa_hip_dl_more queues right after its synchronisation
+    """fa_dl.h DlPost: what fa_hip_dl_more queues right after its synchronisation
     (device plan, trimming decision, slab count) without returning to Python first."""
     _fields_ = [(n, ctypes.c_void_p) for n in ("item_map", "rec", "part", "out")] + \
                [(n, ctypes.c_int64) for n in ("rec_cap", "part_cap", "out_cap")] + \
@@ -1568,10 +1613,11 @@ class DeviceLevelState:
     def __init__(self, dev):
         self.dev = dev
         self.ws = torch.empty(64 << 20, dtype=torch.uint8, device=dev)
-        self.ctl = torch.zeros(DL_CTL, dtype=_I64, device=dev)
-        self.ctl_h = torch.zeros(DL_CTL, dtype=_I64, pin_memory=True)
+        K = dl()
+        self.ctl = torch.zeros(K.kDlCtl, dtype=_I64, device=dev)
+        self.ctl_h = torch.zeros(K.kDlCtl, dtype=_I64, pin_memory=True)
         self.fsz = torch.zeros(128, dtype=_I64, device=dev)
-        self.desc = np.zeros((32, 8), dtype=np.int64)
+        self.desc = np.zeros(K.kDlMaxL, dtype=K.desc_dtype).view(_DescTable)   # fa_dl.h DlDesc [kDlMaxL]
         self.info = np.zeros(4, dtype=np.int64)
         self.post = DlPostC()
         self.post_bufs = None
@@ -1629,9 +1675,10 @@ def dl_bundle_gen(S: DeviceLevelState, P0: int, n_src: int | None, n_const: int,
                   accb: float = 4.0) -> np.ndarray:
     """Candidates of a device bundle: level 0 from F_{k-1} rows P0 and the speculative
     levels 1 .. max_levels-1 (accepted on the device), all queued before ONE
-    synchronisation (accb: LDS bytes per slab accumulator, 2 = packed u16 counters).  Returns the control block (host int64 [DL_CTL]); S.desc[:L]
-    describes the accepted levels (L = ctl[1])."""
-    lib = _native.hip()
+    synchronisation (accb: LDS bytes per slab accumulator, 2 = packed u16 counters).
+    Returns the control block (host int64 [kDlCtl]); S.desc[:L] describes the accepted
+    levels (L = ctl[kDlLevels])."""
+    lib, K = _native.hip(), dl()
     info = np.zeros(2, dtype=np.int64)
     for _ in range(6):
         S.desc[:] = 0
@@ -1642,10 +1689,11 @@ def dl_bundle_gen(S: DeviceLevelState, P0: int, n_src: int | None, n_const: int,
             S.grow(int(S.info[0]))
             continue
         _native.check(rc, "fa_hip_dl_level0")
-        S.desc[0, :5] = [P0, S.info[1], S.info[2], S.info[3], m0]
+        d0 = S.desc[0]
+        d0["P"], d0["cnt"], d0["off"], d0["rows"], d0["m"] = P0, S.info[1], S.info[2], S.info[3], m0
         if max_levels <= 1:
             c = S.ctl_h.numpy()
-            S.desc[0, 5:8] = [c[8], c[40], 0]
+            d0["n"], d0["C"], d0["base"] = c[K.kDlNl], c[K.kDlCl], 0
             return c.copy()
         S.post.done = 0
         lane_deal(lib, S.rows_hint)    # (the post step's plan)
@@ -1685,7 +1733,7 @@ def dl_plan(S: DeviceLevelState, L: int, F1: int, n_used: int, C: int, lds: int,
         raise RuntimeError(f"device bundle of {C} candidates over {n_used} items does not fit one pass")
     item_map = torch.empty(max(F1, 1), dtype=_I32, device=dev)
     rec = torch.empty(12 * C + 12, dtype=_I32, device=dev)
-    R = int(S.desc[:L, 5].sum())                     # parent rows of the bundle
+    R = int(S.desc["n"][:L].sum())                   # parent rows of the bundle
     part = torch.empty(8 * max(1, (R + 255) // 256), dtype=_I32, device=dev)
     lib = _native.hip()
     gn = int(lib.fa_hip_dl_gpre_need(S.desc.ctypes.data, L))
@@ -1734,13 +1782,14 @@ def dl_count_multipass(S: DeviceLevelState, F1: int, n_used: int, C: int, lds: i
     cap = max(w1 - w0 for w0, w1, _, _ in wins)
     item_map = torch.empty(max(F1, 1), dtype=_I32, device=dev)
     rec = torch.empty(12 * cap + 12, dtype=_I32, device=dev)
-    R = int(S.desc[0, 5])
+    R = int(S.desc[0]["n"])
     part = torch.empty(8 * max(1, (R + 255) // 256) + 16, dtype=_I32, device=dev)
     gn = int(lib.fa_hip_dl_gpre_need(S.desc.ctypes.data, 1))
     gpre = torch.empty(max(gn, 1), dtype=_I32, device=dev)
     out = torch.zeros(C, dtype=_I32, device=dev)
     npass, used_sum, rows_sum, trimmed = 0, 0, 0, 0
     lane_deal(lib, ncols)
+    g_dev = _p(S.ctl) + 8 * dl().kDlPiecesI32        # the window plan's piece count
     for w0, w1, wsw, bits in wins:
         nu, rows_w, bits_p, bm_w, ncols_w = n_used, bm_rows, None, bm, ncols
         if bits is not None:
@@ -1759,23 +1808,19 @@ def dl_count_multipass(S: DeviceLevelState, F1: int, n_used: int, C: int, lds: i
                 rows_w = (bmap[used_t] if bmap is not None else used_t).to(_I32).contiguous()
         if ncols_w == 0:
             continue                                     # no row holds k of the window's items
-        W = (ncols_w + 63) // 64
-        dense = wword is None and TUNING.dense_min_rows > 0 and sup_frac * wsw * 64 >= TUNING.dense_min_rows
-        nslabs = (W + wsw - 1) // wsw
         _native.check(lib.fa_hip_dl_plan_window_bits(S.desc.ctypes.data, 1, _p(S.ctl), F1, _p(bits_p), _p(item_map),
                                                      _p(rec), cap, _p(part), part.numel(), _p(gpre), gpre.numel(),
                                                      w0, w1, wsw, st), "fa_hip_dl_plan_window_bits")
-        nacc = (w1 - w0 + 1) // 2 if acc16 else w1 - w0
-        n_wg = _slab_workgroups(nslabs, nu, wsw, nacc, True, 0)
-        _hip_call("fa_hip_count_slab_rec_cls", _p(roff), _p(ranks), _p(src), ncols_w, _p(item_map), F1, nu,
-                  _p(gpre), _p(rec), 0, w1 - w0, _p(wword), out.data_ptr() + 4 * w0, wsw, n_wg, _p(bm_w),
-                  bitmap_ld(bm_w), st, _p(rows_w), _p(S.ctl) + 8 * 221, (2 if dense else 0) | (4 if acc16 else 0))
+        _slab_count(roff=_p(roff), ranks=_p(ranks), src=_p(src), ncols=ncols_w, item_map=_p(item_map), F1=F1,
+                    n_used=nu, gpre=_p(gpre), rec=_p(rec), g_dev=g_dev, C=w1 - w0, wword=_p(wword),
+                    out=out.data_ptr() + 4 * w0, sw=wsw, st=st, round_acc=True, map_bytes=0, bm=_p(bm_w),
+                    bm_ld=bitmap_ld(bm_w), bm_rows=_p(rows_w), accb=accb, sup_frac=sup_frac)
         npass += 1
         used_sum += nu
         rows_sum += ncols_w
     LAST_LEVEL_PLAN.clear()
     LAST_LEVEL_PLAN.update(kernel="slab_dev_multi", rows=int(roff.numel() - 1), used=n_used, sw=sw, cap=cap,
-                           passes=npass, pieces=-1, slab_reads=0, m=int(S.desc[0, 4]), C=C,
+                           passes=npass, pieces=-1, slab_reads=0, m=int(S.desc[0]["m"]), C=C,
                            window_used_avg=round(used_sum / max(npass, 1), 1),
                            window_rows_avg=round(rows_sum / max(npass, 1)), windows_trimmed=trimmed)
     return out
@@ -1837,7 +1882,7 @@ def dl_window_plan(S: DeviceLevelState, F1: int, C: int, lds: int, accb: int, st
     slab width of the rule (slab_width).  Returns [(w0, w1, sw,
     uint64 bitset [nwd])], or None when F1 is too wide for the bitsets."""
     nwd = (F1 + 63) // 64
-    if nwd > 512 or C < 1:
+    if nwd > dl().kDlBitsW or C < 1:
         return None
     nch = -(-C // chunk)
     bits_d = torch.empty(nch * nwd, dtype=_I64, device=dev)
@@ -1881,14 +1926,10 @@ def dl_count(S: DeviceLevelState, plan: dict, roff, ranks, src, ncols: int, F1: 
     st = _stream(ranks)
     sw, cap, n_used, C = plan["sw"], plan["cap"], plan["n_used"], plan["C"]
     item_map, rec, out = plan["item_map"], plan["rec"], plan["out"]
-    W = (ncols + 63) // 64
-    nslabs = (W + sw - 1) // sw
-    acc16 = plan.get("accb", 4.0) == 2.0 and wword is None
-    nacc = (C + 1) // 2 if acc16 else C
-    n_wg = _slab_workgroups(nslabs, n_used, sw, nacc, True, slab_map_lds(F1))
-    _hip_call("fa_hip_count_slab_rec_cls", _p(roff), _p(ranks), _p(src), ncols, _p(item_map), F1, n_used,
-              _p(plan.get("gpre")), _p(rec), 0, C, _p(wword), _p(out), sw, n_wg, None, 0, st, None,
-              _p(S.ctl) + 8 * 221, 4 if acc16 else 0)
+    _slab_count(roff=_p(roff), ranks=_p(ranks), src=_p(src), ncols=ncols, item_map=_p(item_map), F1=F1,
+                n_used=n_used, gpre=_p(plan.get("gpre")), rec=_p(rec), g_dev=_p(S.ctl) + 8 * dl().kDlPiecesI32, C=C,
+                wword=_p(wword), out=_p(out), sw=sw, st=st, round_acc=True, map_bytes=slab_map_lds(F1),
+                accb=plan.get("accb", 4.0))
     LAST_LEVEL_PLAN.clear()
     LAST_LEVEL_PLAN.update(kernel="slab_dev", rows=int(roff.numel() - 1), used=n_used, sw=sw, cap=cap, passes=1,
                            pieces=-1, slab_reads=0, m=-1, C=C)
@@ -1902,8 +1943,8 @@ def dl_threshold(S: DeviceLevelState, L: int, counts: torch.Tensor, mc: int, k0:
     cnt int32 arena, rows_off int64 [L], cnt_off int64 [L]); |F_{k0+l}| lands in
     S.fsz[k0 + l] on the device."""
     dev = counts.device
-    C = S.desc[:L, 6]
-    w = S.desc[:L, 4] + 1
+    C = S.desc["C"][:L]
+    w = S.desc["m"][:L] + 1
     rows_off = np.zeros(L, dtype=np.int64)
     cnt_off = np.zeros(L, dtype=np.int64)
     if L > 1:

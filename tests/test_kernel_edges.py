@@ -411,7 +411,8 @@ def test_dl_threshold(dl_state, Cs, widths, keep, dev):
     rows_t = [torch.from_numpy(r).to(DEV) for r, _ in levels]          # kept alive to the end
     S.desc[:] = 0
     for l, (r, c) in enumerate(levels):
-        S.desc[l] = [0, 0, 0, rows_t[l].data_ptr(), r.shape[1] - 1, 1, c.size, bases[l]]
+        d = S.desc[l]
+        d["rows"], d["m"], d["n"], d["C"], d["base"] = rows_t[l].data_ptr(), r.shape[1] - 1, 1, c.size, bases[l]
     S.fsz.fill_(-1)
     rows, cnt, rows_off, cnt_off = prim.dl_threshold(S, L, counts, mc, k0)
     fsz = S.fsz.cpu().numpy()
