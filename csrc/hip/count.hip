@@ -57,8 +57,6 @@ constexpr int kPW = 16;                // waves per workgroup (1024 threads)
 constexpr int kWSpan = 1024;           // ranks staged per wave batch
 constexpr int kWPer = kWSpan / 64;     // per lane
 
-__device__ __forceinline__ void wave_lds_fence() { wave_lds_sync(); }
-
 // ---------------------------------------------------------------------------
 // k = 2, blocked layout.  Rows are re-laid out per 128-rank block:
 //   cnt[b][x]   u8   number of ranks of row x in block b
@@ -66,11 +64,6 @@ __device__ __forceinline__ void wave_lds_fence() { wave_lds_sync(); }
 //   lr[...]     u8   local ranks (rank - 128*b), block-major, batch-major, row order
 // A tile (bi, bj) then reads two bytes per row and only its two blocks' segments.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
-  (void)lane;
-  return wave_scan_incl_dpp(v);
-}
-
 // one wave per 64-row batch; lane = row
 __global__ __launch_bounds__(256) void k_block_counts(const int64_t* __restrict__ roff,
                                                       const int32_t* __restrict__ ranks, int64_t T, int nb,
@@ -108,7 +101,7 @@ __global__ __launch_bounds__(256) void k_block_scatter(const int64_t* __restrict
   int64_t i = valid ? roff[x] : 0;
   for (int b = 0; b < nb; ++b) {
     const int c = valid ? cnt[(int64_t)b * T + x] : 0;
-    const int incl = wave_incl_scan(c, lane);
+    const int incl = wave_scan_incl_dpp(c);
     int64_t o = base[(int64_t)b * nbatch + q] + (incl - c);
     for (int k = 0; k < c; ++k) lr[o + k] = (uint8_t)(ranks[i + k] - b * pb);
     i += c;
@@ -278,11 +271,11 @@ __global__ __launch_bounds__(1024) void k_pair_blocked(
     if (q + kPW < q1) load(q + kPW, ci_n, cj_n, w_n);
     const int ni = w ? ci : 0, nj = w ? cj : 0;
     const int P = (ni > 0 && nj > 0) ? ni * nj : 0;
-    const int incl = wave_incl_scan(P, lane);
+    const int incl = wave_scan_incl_dpp(P);
     const int total = wave_last(incl);
     if (total > 0) {
-      const int inci = wave_incl_scan(ci, lane);
-      const int incj = diag ? inci : wave_incl_scan(cj, lane);
+      const int inci = wave_scan_incl_dpp(ci);
+      const int incj = diag ? inci : wave_scan_incl_dpp(cj);
       const int tot_i = wave_last(inci), tot_j = wave_last(incj);
       const int64_t bsi = base[(int64_t)bi * nbatch + q];
       const int64_t bsj = base[(int64_t)bj * nbatch + q];
@@ -296,7 +289,7 @@ __global__ __launch_bounds__(1024) void k_pair_blocked(
       mist[lane] = inci - ci;
       mjst[lane] = incj - cj;
       mnw[lane] = nj;
-      wave_lds_fence();
+      wave_lds_sync();
       auto scatter = [&](const uint8_t* __restrict__ A, const uint8_t* __restrict__ B) {
         for (int f = lane; f < total; f += 64) {
           int owner = 0;
@@ -316,7 +309,7 @@ __global__ __launch_bounds__(1024) void k_pair_blocked(
       };
       if (staged) scatter(si, sj);
       else scatter(lr + bsi, lr + bsj);
-      wave_lds_fence();
+      wave_lds_sync();
     }
     ci = ci_n; cj = cj_n; w = w_n;
   }
@@ -743,34 +736,18 @@ __global__ __launch_bounds__(256) void k_pairs_keep_count(const uint32_t* __rest
   const int i = blockIdx.x;
   int c = 0;
   for (int j = i + 1 + threadIdx.x; j < F1; j += 256) c += (int64_t)pc_at(pc, ld, F1, i, j) >= mc;
-  c = (int)wave_sum_u32((uint32_t)c);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) row_cnt[i] = part[0] + part[1] + part[2] + part[3];
+  c = wg_sum<4>(c, part);
+  if (threadIdx.x == 0) row_cnt[i] = c;
 }
 
 // exclusive row offsets (one workgroup), |F_2| into n_out[0]
 __global__ __launch_bounds__(1024) void k_pairs_scan(const int32_t* __restrict__ row_cnt, int F1,
                                                      int64_t* __restrict__ row_off, int64_t* __restrict__ n_out) {
-  __shared__ int64_t part[16];
-  __shared__ int64_t carry;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int b = 0; b < F1; b += 1024) {
-    const int i = b + threadIdx.x;
-    const int v = i < F1 ? row_cnt[i] : 0;
-    const int incl = wave_scan_incl_dpp(v);
-    if (lane == 63) part[wv] = incl;
-    __syncthreads();
-    int64_t before = carry;
-    for (int q = 0; q < wv; ++q) before += part[q];
-    if (i < F1) row_off[i] = before + incl - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry = before + incl;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) n_out[0] = carry;
+  __shared__ int part[16];
+  const int64_t total = wg_scan_chunks<16>(
+      F1, 0, part, [&](int64_t i) { return row_cnt[i]; },
+      [&](int64_t i, int64_t before, int) { row_off[i] = before; });
+  if (threadIdx.x == 0) n_out[0] = total;
 }
 
 // one workgroup per row: its kept pairs in j order at row_off[i]
@@ -778,30 +755,17 @@ __global__ __launch_bounds__(256) void k_pairs_emit(const uint32_t* __restrict__
                                                     const int64_t* __restrict__ row_off, int32_t* __restrict__ rows,
                                                     int32_t* __restrict__ cnt) {
   __shared__ int part[4];
-  __shared__ int64_t carry;
   const int i = blockIdx.x;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry = row_off[i];
-  __syncthreads();
-  for (int j0 = i + 1; j0 < F1; j0 += 256) {
-    const int j = j0 + threadIdx.x;
-    const uint32_t v = j < F1 ? pc_at(pc, ld, F1, i, j) : 0u;
-    const int keep = (j < F1 && (int64_t)v >= mc) ? 1 : 0;
-    const int incl = wave_scan_incl_dpp(keep);
-    if (lane == 63) part[wv] = incl;
-    __syncthreads();
-    int64_t at = carry;
-    for (int q = 0; q < wv; ++q) at += part[q];
-    at += incl - keep;
-    if (keep) {
-      rows[2 * at] = i;
-      rows[2 * at + 1] = j;
-      cnt[at] = (int32_t)v;
-    }
-    __syncthreads();
-    if (threadIdx.x == 255) carry = at + keep;
-    __syncthreads();
-  }
+  uint32_t v;                                      // the pair's count, from load to store
+  wg_scan_chunks<4>(
+      F1 - (i + 1), row_off[i], part,
+      [&](int64_t q) { v = pc_at(pc, ld, F1, i, i + 1 + q); return (int64_t)v >= mc ? 1 : 0; },
+      [&](int64_t q, int64_t at, int keep) {
+        if (!keep) return;
+        rows[2 * at] = i;
+        rows[2 * at + 1] = (int32_t)(i + 1 + q);
+        cnt[at] = (int32_t)v;
+      });
 }
 
 // ---------------------------------------------------------------------------

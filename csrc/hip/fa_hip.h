@@ -52,6 +52,144 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
   return v;
 }
 
+// Inclusive wave64 prefix sum of 64-bit values (shuffles: DPP moves 32 bits).
+__device__ __forceinline__ int64_t wave_scan_incl_i64(int64_t v) {
+  const int lane = (int)(threadIdx.x & 63);
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int64_t t = __shfl_up(v, o, 64);
+    if (lane >= o) v += t;
+  }
+  return v;
+}
+
+// the wave scan / wave sum of a value's own type (what the workgroup forms below build on)
+__device__ __forceinline__ int wave_scan_incl(int v) { return wave_scan_incl_dpp(v); }
+__device__ __forceinline__ int64_t wave_scan_incl(int64_t v) { return wave_scan_incl_i64(v); }
+__device__ __forceinline__ int wave_sum(int v) { return (int)wave_sum_u32((uint32_t)v); }
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) { return wave_sum_u32(v); }
+__device__ __forceinline__ int64_t wave_sum(int64_t v) { return (int64_t)wave_sum_u64((unsigned long long)v); }
+
+// ---------------------------------------------------------------------------
+// Workgroup scans and sums over W waves (blockDim.x = 64 W): every wave leaves its
+// total in LDS, one barrier, every thread adds the totals it needs.  Common contract:
+//   * every thread of the workgroup must reach the call (no early return before it,
+//     no call under a condition that differs inside the workgroup);
+//   * scratch: W * N elements of T in LDS, passed by the caller.  It is written
+//     before the call's barrier and read after it, so it may be written again (by
+//     another call or anything else) only after one more __syncthreads of the
+//     caller's; wg_scan_chunks holds that barrier itself;
+//   * T is the type of the per-wave scan (int: DPP, int64_t: shuffles); the sums
+//     across waves are taken in the type of the results (A), which may be wider.
+// ---------------------------------------------------------------------------
+
+// The step across waves, which the forms below share (use it directly where a wave
+// already has its totals, e.g. from a ballot): lane src of every wave holds the wave's
+// totals x[0 .. N); before[j] = sum of x[j] over the waves before this one, total[j] =
+// the workgroup's sum (the same in every thread).  One __syncthreads, none after the reads.
+template <int W, int N, typename T, typename A>
+__device__ __forceinline__ void wg_wave_prefix(const T (&x)[N], int src, T* scratch, A (&before)[N], A (&total)[N]) {
+  const int lane = (int)(threadIdx.x & 63), w = (int)(threadIdx.x >> 6);
+#pragma unroll
+  for (int j = 0; j < N; ++j)
+    if (lane == src) scratch[j * W + w] = x[j];
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    A bef = 0, tot = 0;
+#pragma unroll 4
+    for (int k = 0; k < W; ++k) {
+      const A t = (A)scratch[j * W + k];
+      bef += k < w ? t : (A)0;
+      tot += t;
+    }
+    before[j] = bef;
+    total[j] = tot;
+  }
+}
+
+// One-shot exclusive scan of N values per thread: excl[j] = sum of v[j] over the
+// threads before this one, total[j] as above.
+template <int W, int N, typename T, typename A>
+__device__ __forceinline__ void wg_scan_excl(const T (&v)[N], T* scratch, A (&excl)[N], A (&total)[N]) {
+  T incl[N];
+#pragma unroll
+  for (int j = 0; j < N; ++j) incl[j] = wave_scan_incl(v[j]);
+  wg_wave_prefix<W>(incl, 63, scratch, excl, total);
+#pragma unroll
+  for (int j = 0; j < N; ++j) excl[j] += (A)incl[j] - (A)v[j];
+}
+
+template <int W, typename T, typename A>
+__device__ __forceinline__ A wg_scan_excl(T v, T* scratch, A& total) {
+  const T v1[1] = {v};
+  A e[1], t[1];
+  wg_scan_excl<W>(v1, scratch, e, t);
+  total = t[0];
+  return e[0];
+}
+
+// Workgroup sums of N values per thread, returned to every thread.
+template <int W, int N, typename T>
+__device__ __forceinline__ void wg_sum(const T (&v)[N], T* scratch, T (&total)[N]) {
+  T s[N], before[N];
+#pragma unroll
+  for (int j = 0; j < N; ++j) s[j] = wave_sum(v[j]);
+  wg_wave_prefix<W>(s, 0, scratch, before, total);
+}
+
+template <int W, typename T>
+__device__ __forceinline__ T wg_sum(T v, T* scratch) {
+  const T v1[1] = {v};
+  T t[1];
+  wg_sum<W>(v1, scratch, t);
+  return t[0];
+}
+
+// Exclusive scan of n elements (N interleaved sequences) by ONE workgroup, in chunks of
+// 64 W elements with an int64 carry.  For every element i < n, in order of the chunks:
+//   load(i, v)            fills v[0 .. N) (T; a chunk's sum per wave must fit T);
+//   store(i, before, v)   before[j] = carry[j] + v[j] of every element < i (int64).
+// Both run in the same thread, load first, so a load may leave what it read in a local
+// that its store uses (a kept element's payload).  On return carry[j] has grown by the
+// whole sum, in every thread.
+// Two __syncthreads per chunk.  The carry lives in registers: every thread adds the
+// same wave totals from scratch, so no thread has to publish it and only scratch is
+// shared -- one barrier between its writes and its reads (wg_scan_excl's), one between
+// those reads and the next chunk's writes.  (Hand-written forms kept the carry in an
+// LDS word written by the last thread, which took a third barrier.)  The trailing
+// barrier also lets the caller reuse scratch, or call again, right after the return.
+template <int W, int N, typename T, class Load, class Store>
+__device__ __forceinline__ void wg_scan_chunks(int64_t n, int64_t (&carry)[N], T* scratch, Load&& load,
+                                               Store&& store) {
+  for (int64_t b0 = 0; b0 < n; b0 += 64 * W) {
+    const int64_t i = b0 + threadIdx.x;
+    T v[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) v[j] = 0;
+    if (i < n) load(i, v);
+    int64_t before[N], total[N];
+    wg_scan_excl<W>(v, scratch, before, total);
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      before[j] += carry[j];
+      carry[j] += total[j];
+    }
+    if (i < n) store(i, before, v);
+    __syncthreads();
+  }
+}
+
+// one sequence: load(i) returns the value, store(i, before, v); returns the final carry
+template <int W, typename T, class Load, class Store>
+__device__ __forceinline__ int64_t wg_scan_chunks(int64_t n, int64_t carry, T* scratch, Load&& load, Store&& store) {
+  int64_t c[1] = {carry};
+  wg_scan_chunks<W, 1>(
+      n, c, scratch, [&](int64_t i, T (&v)[1]) { v[0] = load(i); },
+      [&](int64_t i, const int64_t (&before)[1], const T (&v)[1]) { store(i, before[0], v[0]); });
+  return c[0];
+}
+
 // Orders this wave's LDS accesses across lanes.  The LDS executes one wave's DS
 // instructions in issue order, so a read issued after another lane's write sees
 // it: only the compiler must not reorder or cache them.  (A memory-model fence

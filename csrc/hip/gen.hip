@@ -560,33 +560,33 @@ __global__ __launch_bounds__(256) void k_agd_rows(const int32_t* __restrict__ P,
   }
 }
 
+// exclusive offsets off[0 .. n] of cnt[0 .. n) by one 1024-thread workgroup; returns off[n].
+// kGroups: *groups = rows with cnt > 0, the reference's prefix-group count (genCandidates
+// drops empty groups, FastApriori.scala:189-190); one more barrier
+template <bool kGroups>
+__device__ __forceinline__ int64_t agd_block_scan(const int32_t* __restrict__ cnt, int64_t* __restrict__ off,
+                                                  int64_t n, int64_t* groups = nullptr) {
+  __shared__ int part[16];
+  if (threadIdx.x == 0) off[0] = 0;
+  int nz = 0;
+  const int64_t C = wg_scan_chunks<16>(
+      n, 0, part, [&](int64_t i) { return cnt[i]; },
+      [&](int64_t i, int64_t before, int v) {
+        off[i + 1] = before + v;
+        if (kGroups) nz += v > 0;
+      });
+  if (kGroups) *groups = wg_sum<16>(nz, part);
+  return C;
+}
+
 // off[0 .. n] = exclusive offsets of cnt[0 .. n) (one workgroup), then the acceptance of
 // level l by thread 0: C_l = off[n_l]
 __global__ __launch_bounds__(1024) void k_agd_scan_decide(const int32_t* __restrict__ cnt, int64_t* __restrict__ off,
                                                           long long* __restrict__ c, int l, double growth,
                                                           int64_t c_bound) {
-  __shared__ int64_t part[16];
-  __shared__ int64_t carry;
   if (c[kDlStop]) return;
-  const int64_t n = c[kDlNl + l];
-  if (threadIdx.x == 0) { carry = 0; off[0] = 0; }
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  for (int64_t b = 0; b < n; b += 1024) {
-    const int64_t i = b + threadIdx.x;
-    const int v = i < n ? cnt[i] : 0;
-    const int incl = wave_scan_incl_dpp(v);
-    if (lane == 63) part[wv] = incl;
-    __syncthreads();
-    int64_t before = carry;
-    for (int q = 0; q < wv; ++q) before += part[q];
-    if (i < n) off[i + 1] = before + incl;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry = before + incl;
-    __syncthreads();
-  }
+  const int64_t C = agd_block_scan<false>(cnt, off, c[kDlNl + l]);
   if (threadIdx.x != 0) return;
-  const int64_t C = carry;
   const int64_t total = c[kDlTotal], last = c[kDlLastC], tmax = c[kDlTmax];
   if (C == 0 || (double)C > growth * (double)last || total + C > tmax || C > c_bound) {
     c[kDlStop] = 1;
@@ -708,36 +708,6 @@ static int ag_chain_dev(const int32_t* P1, int64_t n1, int m1, int nw, char* w0,
 // ---------------------------------------------------------------------------
 namespace fa {
 
-__device__ int64_t agd_block_scan(const int32_t* __restrict__ cnt, int64_t* __restrict__ off, int64_t n,
-                                  int64_t* groups = nullptr) {
-  // exclusive offsets off[0 .. n] of cnt[0 .. n) by one 1024-thread workgroup; returns off[n].
-  // groups (thread 0's copy): rows with cnt > 0, the reference's prefix-group count
-  // (genCandidates drops empty groups, FastApriori.scala:189-190)
-  __shared__ int64_t part[16];
-  __shared__ int64_t carry;
-  __shared__ unsigned int nz;
-  if (threadIdx.x == 0) { carry = 0; off[0] = 0; nz = 0u; }
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  for (int64_t b = 0; b < n; b += 1024) {
-    const int64_t i = b + threadIdx.x;
-    const int v = i < n ? cnt[i] : 0;
-    const int incl = wave_scan_incl_dpp(v);
-    const unsigned long long had = __ballot(v > 0);
-    if (lane == 0 && had) atomicAdd(&nz, (unsigned int)__popcll(had));
-    if (lane == 63) part[wv] = incl;
-    __syncthreads();
-    int64_t before = carry;
-    for (int q = 0; q < wv; ++q) before += part[q];
-    if (i < n) off[i + 1] = before + incl;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry = before + incl;
-    __syncthreads();
-  }
-  if (groups && threadIdx.x == 0) *groups = (int64_t)nz;
-  return carry;
-}
-
 // ctl[kDlOverBound] = 1: the device row count n_src[0] exceeds n_bound (the buffers' size):
 // nothing runs and the host raises
 __global__ __launch_bounds__(kDlCtl) void k_dl_setup0(long long* __restrict__ c, const long long* __restrict__ n_src,
@@ -759,7 +729,7 @@ __global__ __launch_bounds__(1024) void k_dl_decide0(const int32_t* __restrict__
                                                       long long* __restrict__ c, int64_t c_bound) {
   if (c[kDlStop]) return;
   int64_t g = 0;
-  const int64_t C = agd_block_scan(cnt, off, c[kDlNl], &g);
+  const int64_t C = agd_block_scan<true>(cnt, off, c[kDlNl], &g);
   if (threadIdx.x != 0) return;
   c[kDlCl] = C;
   c[kDlGl] = g;
@@ -785,9 +755,7 @@ __global__ __launch_bounds__(1024) void k_ds_blocks(const int32_t* __restrict__ 
     if (threadIdx.x == 0) { bs[blockIdx.x] = 0; bs[nblk + blockIdx.x] = 0; }
     return;
   }
-  __shared__ int wpart[16];
-  __shared__ int wnz[16];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  __shared__ int wpart[2 * 16];
   // four consecutive rows per thread, in order
   int v[4], t = 0, nz = 0;
 #pragma unroll
@@ -797,13 +765,10 @@ __global__ __launch_bounds__(1024) void k_ds_blocks(const int32_t* __restrict__ 
     t += v[u];
     nz += v[u] > 0;
   }
-  const int incl = wave_scan_incl_dpp(t);
-  const int nzs = (int)wave_sum_u32((uint32_t)nz);
-  if (lane == 63) wpart[wv] = incl;
-  if (lane == 0) wnz[wv] = nzs;
-  __syncthreads();
-  int64_t run = incl - t;
-  for (int q = 0; q < wv; ++q) run += wpart[q];
+  const int tz[2] = {t, nz};
+  int64_t pre[2], tot[2];                          // (one barrier for both; nz's prefix is unused)
+  wg_scan_excl<16>(tz, wpart, pre, tot);
+  int64_t run = pre[0];
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     const int64_t i = b0 + 4 * (int64_t)threadIdx.x + u;
@@ -811,10 +776,8 @@ __global__ __launch_bounds__(1024) void k_ds_blocks(const int32_t* __restrict__ 
     if (i < n) off[i + 1] = run;
   }
   if (threadIdx.x == 0) {
-    int64_t tot = 0, z = 0;
-    for (int q = 0; q < 16; ++q) { tot += wpart[q]; z += wnz[q]; }
-    bs[blockIdx.x] = tot;
-    bs[nblk + blockIdx.x] = z;
+    bs[blockIdx.x] = tot[0];
+    bs[nblk + blockIdx.x] = tot[1];
   }
 }
 
@@ -822,34 +785,17 @@ __global__ __launch_bounds__(1024) void k_ds_decide0(int64_t* __restrict__ off, 
                                                      int64_t* __restrict__ bs, int nblk, int64_t c_bound) {
   if (c[kDlStop]) return;
   __shared__ int64_t part[16];
-  __shared__ int64_t carry, gz;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (threadIdx.x == 0) { carry = 0; gz = 0; off[0] = 0; }
-  __syncthreads();
-  for (int q0 = 0; q0 < nblk; q0 += 1024) {
-    const int q = q0 + threadIdx.x;
-    const int64_t v = q < nblk ? bs[q] : 0;
-    const int64_t z = q < nblk ? bs[nblk + q] : 0;
-    // 64-bit inclusive scan by shuffles (block totals can pass 2^31 only in theory; cheap here)
-    int64_t incl = v;
-    for (int d = 1; d < 64; d <<= 1) {
-      const int64_t o = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += o;
-    }
-    int64_t zs = z;
-    for (int d = 32; d > 0; d >>= 1) zs += __shfl_xor(zs, d, 64);
-    if (lane == 63) part[wv] = incl;
-    __syncthreads();
-    int64_t before = carry;
-    for (int k = 0; k < wv; ++k) before += part[k];
-    if (q < nblk) bs[2 * nblk + q] = before + incl - v;     // exclusive block base
-    if (lane == 0) atomicAdd((unsigned long long*)&gz, (unsigned long long)zs);
-    __syncthreads();
-    if (threadIdx.x == 1023) carry = before + incl;
-    __syncthreads();
-  }
+  if (threadIdx.x == 0) off[0] = 0;
+  // 64-bit scan (block totals can pass 2^31 only in theory; cheap here)
+  int64_t z = 0;
+  const int64_t C = wg_scan_chunks<16>(
+      nblk, 0, part, [&](int64_t q) { return bs[q]; },
+      [&](int64_t q, int64_t before, int64_t) {
+        bs[2 * nblk + q] = before;                           // exclusive block base
+        z += bs[nblk + q];
+      });
+  const int64_t gz = wg_sum<16>(z, part);
   if (threadIdx.x != 0) return;
-  const int64_t C = carry;
   c[kDlCl] = C;
   c[kDlGl] = gz;
   if (C == 0) { c[kDlEnd] = 1; c[kDlStop] = 1; return; }
@@ -911,7 +857,7 @@ __global__ __launch_bounds__(1024) void k_dl_decide(const int32_t* __restrict__ 
                                                      double lds, double accb) {
   if (c[kDlStop]) return;
   int64_t g = 0;
-  const int64_t C = agd_block_scan(cnt, off, c[kDlNl + l], &g);
+  const int64_t C = agd_block_scan<true>(cnt, off, c[kDlNl + l], &g);
   if (threadIdx.x != 0) return;
   const int64_t total = c[kDlTotal], last = c[kDlLastC];
   if (C == 0 || (double)C > growth * (double)last || C > c_bound ||

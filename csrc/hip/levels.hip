@@ -102,21 +102,17 @@ __device__ __forceinline__ int dl_row_count(const DlLevels& D, int64_t t, int64_
 
 // part[blk * 8 + (b - 1)]: pieces of bucket b in block blk
 __global__ __launch_bounds__(kDlPB) void k_dl_pieces_count(const DlLevels D, int32_t* __restrict__ part) {
-  __shared__ int sh[kDlPB / 64][8];
+  __shared__ int sh[8 * (kDlPB / 64)];
   const int64_t R = D.rbase[D.L];
   const int64_t t = (int64_t)blockIdx.x * kDlPB + threadIdx.x;
   const int cc = dl_row_count(D, t, R);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  int v[8], tot[8];
 #pragma unroll
-  for (int b = 1; b <= 8; ++b) {
-    const int tot = wave_last(wave_scan_incl_dpp(dl_bucket_count(cc, b)));
-    if (lane == 0) sh[wv][b - 1] = tot;
-  }
-  __syncthreads();
-  if (threadIdx.x < 8) {
-    int s = 0;
-    for (int w = 0; w < kDlPB / 64; ++w) s += sh[w][threadIdx.x];
-    part[(int64_t)blockIdx.x * 8 + threadIdx.x] = s;
+  for (int b = 1; b <= 8; ++b) v[b - 1] = dl_bucket_count(cc, b);
+  wg_sum<kDlPB / 64>(v, sh, tot);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int b = 0; b < 8; ++b) part[(int64_t)blockIdx.x * 8 + b] = tot[b];
   }
 }
 
@@ -125,25 +121,11 @@ __global__ __launch_bounds__(kDlPB) void k_dl_pieces_count(const DlLevels D, int
 __global__ __launch_bounds__(1024) void k_dl_pieces_scan(int32_t* __restrict__ part, int64_t nblk,
                                                          long long* __restrict__ c) {
   __shared__ int wsum[16];
-  __shared__ int64_t carry;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int b = 8; b >= 1; --b) {
-    for (int64_t b0 = 0; b0 < nblk; b0 += 1024) {
-      const int64_t k = b0 + threadIdx.x;
-      const int v = k < nblk ? part[k * 8 + (b - 1)] : 0;
-      const int incl = wave_scan_incl_dpp(v);
-      if (lane == 63) wsum[wv] = incl;
-      __syncthreads();
-      int64_t before = carry;
-      for (int q = 0; q < wv; ++q) before += wsum[q];
-      if (k < nblk) part[k * 8 + (b - 1)] = (int32_t)(before + incl - v);
-      __syncthreads();
-      if (threadIdx.x == 1023) carry = before + incl;
-      __syncthreads();
-    }
-  }
+  int64_t carry = 0;                               // runs on from bucket to bucket
+  for (int b = 8; b >= 1; --b)
+    carry = wg_scan_chunks<16>(
+        nblk, carry, wsum, [&](int64_t k) { return part[k * 8 + (b - 1)]; },
+        [&](int64_t k, int64_t before, int) { part[k * 8 + (b - 1)] = (int32_t)before; });
   if (threadIdx.x == 0) {
     c[kDlPieces] = carry;
     reinterpret_cast<int32_t*>(c + kDlPiecesI32)[0] = (int32_t)carry;
@@ -175,29 +157,19 @@ __device__ __forceinline__ void dl_write_rec(int4* __restrict__ rec, int64_t p, 
 __global__ __launch_bounds__(kDlPB) void k_dl_pieces_emit(const DlLevels D, const int32_t* __restrict__ part,
                                                           const int32_t* __restrict__ item_map,
                                                           int4* __restrict__ rec) {
-  __shared__ int sh[kDlPB / 64][8];
+  __shared__ int sh[8 * (kDlPB / 64)];
   const int64_t R = D.rbase[D.L];
   const int64_t t = (int64_t)blockIdx.x * kDlPB + threadIdx.x;
   int64_t first = 0;
   const int cc = dl_row_window(D, t, R, &first);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  int excl[9];
+  int v[8], excl[8], tot[8];
 #pragma unroll
-  for (int b = 1; b <= 8; ++b) {
-    const int v = dl_bucket_count(cc, b);
-    const int incl = wave_scan_incl_dpp(v);
-    excl[b] = incl - v;
-    if (lane == 63) sh[wv][b - 1] = incl;
-  }
-  __syncthreads();
+  for (int b = 1; b <= 8; ++b) v[b - 1] = dl_bucket_count(cc, b);
+  wg_scan_excl<kDlPB / 64>(v, sh, excl, tot);
   if (cc == 0) return;
   int64_t slot[9];
 #pragma unroll
-  for (int b = 1; b <= 8; ++b) {
-    int before = 0;
-    for (int q = 0; q < wv; ++q) before += sh[q][b - 1];
-    slot[b] = (int64_t)part[(int64_t)blockIdx.x * 8 + (b - 1)] + before + excl[b];
-  }
+  for (int b = 1; b <= 8; ++b) slot[b] = (int64_t)part[(int64_t)blockIdx.x * 8 + (b - 1)] + excl[b - 1];
   const int l = dl_level_of(D, t);
   const int64_t i = t - D.rbase[l];
   const int m = D.m[l];
@@ -392,37 +364,21 @@ __global__ __launch_bounds__(1024) void k_dl_threshold(const DlLevels D, const D
                                                        int32_t* __restrict__ rows_out, int32_t* __restrict__ cnt_out,
                                                        long long* __restrict__ fsz) {
   __shared__ int part[16];
-  __shared__ int64_t carry;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   for (int l = 0; l < D.L; ++l) {
-    const int64_t C = D.C[l];
     const int w = D.m[l] + 1;
     const uint32_t* cl = counts + D.base[l];
     const int32_t* src = D.rows[l];
     int32_t* ro = rows_out + O.rows_off[l];
     int32_t* co = cnt_out + O.cnt_off[l];
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int64_t b0 = 0; b0 < C; b0 += 1024) {
-      const int64_t e = b0 + threadIdx.x;
-      const uint32_t v = e < C ? cl[e] : 0u;
-      const int keep = (e < C && (int64_t)v >= mc) ? 1 : 0;
-      const int incl = wave_scan_incl_dpp(keep);
-      if (lane == 63) part[wv] = incl;
-      __syncthreads();
-      int64_t at = carry;
-      for (int q = 0; q < wv; ++q) at += part[q];
-      at += incl - keep;
-      if (keep) {
-        co[at] = (int32_t)v;
-        for (int q = 0; q < w; ++q) ro[at * w + q] = src[e * w + q];
-      }
-      __syncthreads();
-      if (threadIdx.x == 1023) carry = at + keep;
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) fsz[l] = carry;
-    __syncthreads();
+    uint32_t v;                                    // the candidate's count, from load to store
+    const int64_t kept = wg_scan_chunks<16>(
+        D.C[l], 0, part, [&](int64_t e) { v = cl[e]; return (int64_t)v >= mc ? 1 : 0; },
+        [&](int64_t e, int64_t at, int keep) {
+          if (!keep) return;
+          co[at] = (int32_t)v;
+          for (int q = 0; q < w; ++q) ro[at * w + q] = src[e * w + q];
+        });
+    if (threadIdx.x == 0) fsz[l] = kept;
   }
 }
 
@@ -456,36 +412,19 @@ __global__ __launch_bounds__(256) void k_dlt_count(const DlLevels D, const DlThr
     k += (e < C && (int64_t)cl[e] >= mc) ? 1u : 0u;
   }
   __shared__ uint32_t ws[4];
-  k = wave_sum_u32(k);
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = k;
-  __syncthreads();
-  if (threadIdx.x == 0) part[b] = (int32_t)(ws[0] + ws[1] + ws[2] + ws[3]);
+  k = wg_sum<4>(k, ws);
+  if (threadIdx.x == 0) part[b] = (int32_t)k;
 }
 
 __global__ __launch_bounds__(1024) void k_dlt_scan(const DlThrBlk B, int L, int32_t* __restrict__ part,
                                                   long long* __restrict__ fsz) {
-  __shared__ int64_t wpart[16];
-  __shared__ int64_t carry;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  __shared__ int wpart[16];
   for (int l = 0; l < L; ++l) {
-    const int64_t b0 = B.blk_base[l], b1 = B.blk_base[l + 1];
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int64_t q = b0; q < b1; q += 1024) {
-      const int64_t i = q + threadIdx.x;
-      const int v = i < b1 ? part[i] : 0;
-      const int incl = wave_scan_incl_dpp(v);
-      if (lane == 63) wpart[wv] = incl;
-      __syncthreads();
-      int64_t before = carry;
-      for (int k = 0; k < wv; ++k) before += wpart[k];
-      if (i < b1) part[i] = (int32_t)(before + incl - v);
-      __syncthreads();
-      if (threadIdx.x == 1023) carry = before + incl;
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) fsz[l] = carry;
-    __syncthreads();
+    int32_t* pl = part + B.blk_base[l];            // the level's blocks; the carry restarts per level
+    const int64_t kept = wg_scan_chunks<16>(
+        B.blk_base[l + 1] - B.blk_base[l], 0, wpart, [&](int64_t i) { return pl[i]; },
+        [&](int64_t i, int64_t before, int) { pl[i] = (int32_t)before; });
+    if (threadIdx.x == 0) fsz[l] = kept;
   }
 }
 
@@ -509,13 +448,8 @@ __global__ __launch_bounds__(256) void k_dlt_emit(const DlLevels D, const DlOut 
     v[u] = e < C ? cl[e] : 0u;
     k += (e < C && (int64_t)v[u] >= mc) ? 1 : 0;
   }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int incl = wave_scan_incl_dpp(k);
-  if (lane == 63) wsum[wv] = incl;
-  __syncthreads();
-  int pos = incl - k;
-  for (int q = 0; q < wv; ++q) pos += wsum[q];
-  const int nk = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  int nk;
+  int pos = wg_scan_excl<4>(k, wsum, nk);
   const int64_t at0 = part[b];
   int32_t* co = cnt_out + O.cnt_off[l];
 #pragma unroll

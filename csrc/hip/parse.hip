@@ -66,14 +66,8 @@ __global__ __launch_bounds__(kLT) void k_line_count(const uint8_t* __restrict__ 
                                                     int32_t* __restrict__ tile_cnt) {
   __shared__ int part[kLT / kWave];
   const int64_t base = (int64_t)blockIdx.x * kLTile + (int64_t)threadIdx.x * kLB;
-  const uint32_t c = wave_sum_u32((uint32_t)scan_bytes<0>(buf, n, base, nullptr));
-  if (lane_id() == 0) part[threadIdx.x >> 6] = (int)c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int t = 0;
-    for (int w = 0; w < kLT / kWave; ++w) t += part[w];
-    tile_cnt[blockIdx.x] = t;
-  }
+  const int t = wg_sum<kLT / kWave>(scan_bytes<0>(buf, n, base, nullptr), part);
+  if (threadIdx.x == 0) tile_cnt[blockIdx.x] = t;
 }
 
 __global__ __launch_bounds__(kLT) void k_line_ends(const uint8_t* __restrict__ buf, int64_t n,
@@ -82,12 +76,9 @@ __global__ __launch_bounds__(kLT) void k_line_ends(const uint8_t* __restrict__ b
   __shared__ int part[kLT / kWave];
   const int64_t base = (int64_t)blockIdx.x * kLTile + (int64_t)threadIdx.x * kLB;
   const int mine = scan_bytes<0>(buf, n, base, nullptr);
-  const int incl = wave_scan_incl_dpp(mine);
-  if (lane_id() == 63) part[threadIdx.x >> 6] = incl;
-  __syncthreads();
-  int before = 0;
-  for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) before += part[w];
-  if (mine) scan_bytes<1>(buf, n, base, ends + tile_base[blockIdx.x] + before + incl - mine);
+  int total;
+  const int before = wg_scan_excl<kLT / kWave>(mine, part, total);
+  if (mine) scan_bytes<1>(buf, n, base, ends + tile_base[blockIdx.x] + before);
 }
 
 __global__ __launch_bounds__(256) void k_compact_lines(
@@ -147,14 +138,8 @@ __global__ __launch_bounds__(kLT) void k_tline_count(const uint8_t* __restrict__
                                                      int64_t hi, int32_t* __restrict__ tile_cnt) {
   __shared__ int part[kLT / kWave];
   const int64_t base = a + (int64_t)blockIdx.x * kLTile + (int64_t)threadIdx.x * kLB;
-  const uint32_t c = wave_sum_u32((uint32_t)scan_bytes<0>(buf, hi, base, nullptr, lo));
-  if (lane_id() == 0) part[threadIdx.x >> 6] = (int)c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int t = 0;
-    for (int w = 0; w < kLT / kWave; ++w) t += part[w];
-    tile_cnt[blockIdx.x] = t;
-  }
+  const int t = wg_sum<kLT / kWave>(scan_bytes<0>(buf, hi, base, nullptr, lo), part);
+  if (threadIdx.x == 0) tile_cnt[blockIdx.x] = t;
 }
 
 __global__ __launch_bounds__(kTT) void k_tparse(const uint8_t* __restrict__ buf, int64_t buf_len, int64_t a,
@@ -357,35 +342,26 @@ template <int K>
 __global__ __launch_bounds__(1024) void k_scan_small(const int32_t* __restrict__ in, int64_t n,
                                                      int64_t* __restrict__ out, const int64_t* base,
                                                      int64_t* total) {
-  __shared__ int64_t part[16][K];
-  __shared__ int64_t carry[K];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (threadIdx.x < K) carry[threadIdx.x] = base ? base[threadIdx.x] : 0;
-  __syncthreads();
-  for (int64_t b0 = 0; b0 < n; b0 += 1024) {
-    const int64_t i = b0 + threadIdx.x;
-    int v[K], incl[K];
+  __shared__ int part[16 * K];
+  int64_t carry[K];                                // (base is read before total is written)
+#pragma unroll
+  for (int k = 0; k < K; ++k) carry[k] = base ? base[k] : 0;
+  wg_scan_chunks<16>(
+      n, carry, part,
+      [&](int64_t i, int (&v)[K]) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) v[k] = in[K * i + k];
+      },
+      [&](int64_t i, const int64_t (&before)[K], const int (&)[K]) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) out[K * i + k] = before[k];
+      });
+  if (threadIdx.x == 0) {
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-      v[k] = i < n ? in[K * i + k] : 0;
-      incl[k] = wave_scan_incl_dpp(v[k]);
-      if (lane == 63) part[wv][k] = incl[k];
+      out[K * n + k] = carry[k];
+      if (total) total[k] = carry[k];
     }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      int64_t before = carry[k];
-      for (int q = 0; q < wv; ++q) before += part[q][k];
-      if (i < n) out[K * i + k] = before + incl[k] - v[k];
-      if (threadIdx.x == 1023) part[15][k] = before + incl[k];   // (read after the barrier below)
-    }
-    __syncthreads();
-    if (threadIdx.x < K) carry[threadIdx.x] = part[15][threadIdx.x];
-    __syncthreads();
-  }
-  if (threadIdx.x < K) {
-    out[K * n + threadIdx.x] = carry[threadIdx.x];
-    if (total) total[threadIdx.x] = carry[threadIdx.x];
   }
 }
 
@@ -406,11 +382,11 @@ __global__ __launch_bounds__(256) void k_tcompact(const int64_t* __restrict__ ti
                                                   int64_t* __restrict__ off, unsigned long long* __restrict__ hpart,
                                                   int32_t* __restrict__ flags) {
   __shared__ uint32_t h[kHistCap];
-  __shared__ int wsum[4][2];
+  __shared__ int wsum[2 * 4];
   if (hpart)
     for (int b = threadIdx.x; b < kHistCap; b += 256) h[b] = 0u;
   __syncthreads();
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
   bool over = false, xover = false;
   for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
     // (the region's unterminated last line, when tail, belongs to its last tile)
@@ -422,13 +398,10 @@ __global__ __launch_bounds__(256) void k_tcompact(const int64_t* __restrict__ ti
       int64_t lb = 0;
       if (j < j1) { d = dcnt[j]; x = xcnt[j]; lb = lbase[j]; }
       const int incl = wave_scan_incl_dpp(d);
-      const int xincl = wave_scan_incl_dpp(x);
-      if (lane == 63) { wsum[wv][0] = incl; wsum[wv][1] = xincl; }
-      __syncthreads();
-      int64_t bd = ib, bx = xb;
-      for (int q = 0; q < wv; ++q) { bd += wsum[q][0]; bx += wsum[q][1]; }
-      int64_t td = 0, tx = 0;
-      for (int q = 0; q < 4; ++q) { td += wsum[q][0]; tx += wsum[q][1]; }
+      const int ix[2] = {incl, wave_scan_incl_dpp(x)};
+      int wb[2], tdx[2];                         // ids / repeats of the waves before, and of the chunk
+      wg_wave_prefix<4>(ix, 63, wsum, wb, tdx);
+      const int64_t bd = ib + wb[0];
       if (j < j1) off[j] = bd + incl - d;
       const int tot = wave_last(incl);
       const int excl = incl - d;
@@ -460,7 +433,7 @@ __global__ __launch_bounds__(256) void k_tcompact(const int64_t* __restrict__ ti
         }
       }
       if (x > 0) {                               // repeated ids of the line (rare)
-        const int64_t xo = bx + xincl - x;
+        const int64_t xo = xb + wb[1] + ix[1] - x;
         for (int q = 0; q < x; ++q) {
           const int32_t id = xscratch[lb + q];
           if (xo + q < xcap) extras[xo + q] = id; else xover = true;
@@ -469,8 +442,8 @@ __global__ __launch_bounds__(256) void k_tcompact(const int64_t* __restrict__ ti
           }
         }
       }
-      ib += td;
-      xb += tx;
+      ib += tdx[0];
+      xb += tdx[1];
       __syncthreads();                           // wsum is reused by the next chunk
     }
   }

@@ -104,10 +104,8 @@ __global__ __launch_bounds__(256) void k_f1_rank(const int64_t* __restrict__ his
     }
   }
   if (blockIdx.x == 0) {
-    mine = (int)wave_sum_u32((uint32_t)mine);
-    if ((threadIdx.x & 63) == 0) nf[threadIdx.x >> 6] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) pack[0] = (int64_t)nf[0] + nf[1] + nf[2] + nf[3];
+    mine = wg_sum<4>(mine, nf);
+    if (threadIdx.x == 0) pack[0] = (int64_t)mine;
   }
 }
 
@@ -572,10 +570,8 @@ __global__ __launch_bounds__(256) void k_dedup_probe(const int64_t* __restrict__
   }
   if (x < n_max) slots[x] = slot;
   __shared__ uint32_t wsum[4];
-  const uint32_t c = wave_sum_u32(slot != kNoSlot ? 1u : 0u);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  const uint32_t c = wg_sum<4>(slot != kNoSlot ? 1u : 0u, wsum);
+  if (threadIdx.x == 0) part[blockIdx.x] = c;
 }
 
 // Pass 2: workgroup j owns slots [j * kProbeRange, (j + 1) * kProbeRange) as an LDS
@@ -586,7 +582,7 @@ __global__ __launch_bounds__(1024) void k_probe_count(const uint32_t* __restrict
                                                       const uint32_t* __restrict__ part, int nparts,
                                                       unsigned long long* __restrict__ out) {
   __shared__ uint32_t bits[kProbeRange / 32];
-  __shared__ uint32_t wsum[16];
+  __shared__ uint32_t wsum[2 * 16];
   for (int i = threadIdx.x; i < kProbeRange / 32; i += 1024) bits[i] = 0u;
   __syncthreads();
   const uint32_t lo = (uint32_t)blockIdx.x * kProbeRange;
@@ -616,23 +612,12 @@ __global__ __launch_bounds__(1024) void k_probe_count(const uint32_t* __restrict
   for (int i = threadIdx.x; i < kProbeRange / 32; i += 1024) c += __popc(bits[i]);
   if (blockIdx.x == 0)
     for (int i = threadIdx.x; i < nparts; i += 1024) h += part[i];
-  c = wave_sum_u32(c);
-  h = wave_sum_u32(h);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) wsum[w] = c;
-  __syncthreads();
+  const uint32_t ch[2] = {c, h};
+  uint32_t t[2];
+  wg_sum<16>(ch, wsum, t);
   if (threadIdx.x == 0) {
-    uint32_t t = 0;
-    for (int k = 0; k < 16; ++k) t += wsum[k];
-    if (t) atomicAdd(out, (unsigned long long)t);
-  }
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) wsum[w] = h;
-  __syncthreads();
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    uint32_t t = 0;
-    for (int k = 0; k < 16; ++k) t += wsum[k];
-    out[1] = t;
+    if (t[0]) atomicAdd(out, (unsigned long long)t[0]);
+    if (blockIdx.x == 0) out[1] = t[1];
   }
 }
 
@@ -704,19 +689,6 @@ __global__ __launch_bounds__(256) void k_build_bitmaps(
 //          written without any staging buffer.
 // Rows are dropped when they keep < min_len items (or weight 0).
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ int block_excl_scan256(int v, int* wtot, int* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int incl = wave_scan_incl_dpp(v);
-  if (lane == 63) wtot[w] = incl;
-  __syncthreads();
-  int before = 0, tot = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { before += k < w ? wtot[k] : 0; tot += wtot[k]; }
-  __syncthreads();
-  *total = tot;
-  return before + incl - v;
-}
-
 __device__ __forceinline__ unsigned long long lane_range(int lo, int hi) {   // bits [lo, hi), 0 <= lo, hi <= 64
   const unsigned long long h = hi >= 64 ? ~0ull : ((1ull << hi) - 1);
   const unsigned long long l = lo >= 64 ? ~0ull : ((1ull << lo) - 1);
@@ -779,8 +751,10 @@ __global__ __launch_bounds__(256) void k_trim_scan_count(const int64_t* __restri
   const bool keep = row < T && c >= min_len && (!wrow || wrow[row] > 0);
   if (row < T) cnt[row] = keep ? c : -1;
   int tr, tn;
-  (void)block_excl_scan256(keep ? 1 : 0, wtot, &tr);
-  (void)block_excl_scan256(keep ? c : 0, wtot, &tn);
+  (void)wg_scan_excl<4>(keep ? 1 : 0, wtot, tr);
+  __syncthreads();                               // wtot is used again
+  (void)wg_scan_excl<4>(keep ? c : 0, wtot, tn);
+  __syncthreads();
   if (threadIdx.x == 0) { bk_rows[blockIdx.x] = tr; bk_nnz[blockIdx.x] = tn; }
 }
 
@@ -807,8 +781,10 @@ __global__ __launch_bounds__(256) void k_trim_emit(const int64_t* __restrict__ r
   const int32_t c = row < T ? cnt[row] : -1;
   const bool keep = c >= 0;
   int nk, nn;
-  const int rk = block_excl_scan256(keep ? 1 : 0, wtot, &nk);     // (contains __syncthreads)
-  const int ok = block_excl_scan256(keep ? c : 0, wtot, &nn);
+  const int rk = wg_scan_excl<4>(keep ? 1 : 0, wtot, nk);         // (contains __syncthreads)
+  __syncthreads();                                                 // wtot is used again
+  const int ok = wg_scan_excl<4>(keep ? c : 0, wtot, nn);
+  __syncthreads();
   const int64_t obase = base_nnz[blockIdx.x] + ok;                 // this row's first new slot
   if (keep) {
     nroff[base_rows[blockIdx.x] + rk] = obase;
@@ -869,20 +845,6 @@ __global__ __launch_bounds__(256) void k_trim_emit(const int64_t* __restrict__ r
 //                        through LDS for coalesced stores; longer rows are
 //                        appended to an overflow list for the next tiers.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void cmp_block_scan2(int a, int b, int& ea, int& eb, int& ta, int& tb, int* sh) {
-  // exclusive scans of a and b over the 256-thread workgroup (4 waves)
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int ia = wave_scan_incl_dpp(a), ib = wave_scan_incl_dpp(b);
-  if (lane == 63) { sh[w] = ia; sh[4 + w] = ib; }
-  __syncthreads();
-  int pa = 0, pb = 0;
-  for (int k = 0; k < w; ++k) { pa += sh[k]; pb += sh[4 + k]; }
-  ta = sh[0] + sh[1] + sh[2] + sh[3];
-  tb = sh[4] + sh[5] + sh[6] + sh[7];
-  ea = pa + ia - a;
-  eb = pb + ib - b;
-}
-
 // Loads the workgroup's span into LDS as mapped ranks (0xFFFFFFFF = not frequent).
 // 16 KB spans (4096 tokens per 256 rows: every T10I4 workgroup) keep 8
 // workgroups resident per CU, which hides the dependent offset -> token -> LUT
@@ -1001,17 +963,19 @@ __global__ __launch_bounds__(256) void k_cmp_agg(const int64_t* __restrict__ off
   }
   const int kept = c >= 2;
   if (aggb) cmp_block_totals(kept ? pc : 0ull, nb, aggb);
-  int ea, eb, ta, tb;
-  cmp_block_scan2(kept, kept ? c : 0, ea, eb, ta, tb, sh);
+  const int kc[2] = {kept, kept ? c : 0};        // kept rows, their items
+  int ex[2], tot[2];
+  wg_scan_excl<4>(kc, sh, ex, tot);
   if (kept) atomicAdd(&lh[min(c, 255)], 1u);
   const bool mid = cmp_mid(kept, e - s, staged);
   const unsigned long long ob = __ballot(kept && e - s > kCmpN && !mid);
   __shared__ int ov_w[4];
-  if ((threadIdx.x & 63) == 0) ov_w[threadIdx.x >> 6] = __popcll(ob);
-  __syncthreads();
+  const int ovn[1] = {(int)__popcll(ob)};
+  int ovp[1], ovt[1];
+  wg_wave_prefix<4>(ovn, 0, ov_w, ovp, ovt);
   if (threadIdx.x == 0) {
-    agg[3 * blockIdx.x] = ta; agg[3 * blockIdx.x + 1] = tb;
-    agg[3 * blockIdx.x + 2] = ov_w[0] + ov_w[1] + ov_w[2] + ov_w[3];
+    agg[3 * blockIdx.x] = tot[0]; agg[3 * blockIdx.x + 1] = tot[1];
+    agg[3 * blockIdx.x + 2] = ovt[0];
   }
   // striped histogram copies: 390K workgroups adding into one 256-bin row would
   // serialise on a few hot addresses (~10 distinct row lengths)
@@ -1067,15 +1031,18 @@ __global__ __launch_bounds__(256) void k_cmp_emit(const int64_t* __restrict__ of
   const int kept = c >= 2;
   const bool mid = cmp_mid(kept, L, staged);
   const int ov = kept && L > N && !mid;
-  int ea, eb, ta, tb;
-  cmp_block_scan2(kept, kept ? c : 0, ea, eb, ta, tb, sh);
+  const int kc[2] = {kept, kept ? c : 0};        // kept rows, their items
+  int ex[2], tot[2];
+  wg_scan_excl<4>(kc, sh, ex, tot);
+  const int ea = ex[0], eb = ex[1], tb = tot[1];
   // overflow rows go to their slot of the scanned per-workgroup counts (no atomics:
   // a counter shared by every workgroup serialises), ballot ranks inside the waves
   __shared__ int ov_w[4];
   const int w = threadIdx.x >> 6;
   const unsigned long long ob = __ballot(ov);
-  if ((threadIdx.x & 63) == 0) ov_w[w] = __popcll(ob);
-  __syncthreads();
+  const int ovn[1] = {(int)__popcll(ob)};
+  int64_t ovp[1], ovt[1];                          // overflow rows of the waves before
+  wg_wave_prefix<4>(ovn, 0, ov_w, ovp, ovt);
   const int64_t ov_base = pre_over[blockIdx.x];
   const int64_t xk = xr0 + ea;
   int64_t ovi = -1;
@@ -1083,9 +1050,7 @@ __global__ __launch_bounds__(256) void k_cmp_emit(const int64_t* __restrict__ of
     kept_out[xk] = (int32_t)r;
     roff[xk + 1] = obase + eb + c;
     if (ov) {
-      int64_t before = ov_base;
-      for (int k = 0; k < w; ++k) before += ov_w[k];
-      ovi = before + __popcll(ob & (lanes_le_mask() >> 1));
+      ovi = ov_base + ovp[0] + __popcll(ob & (lanes_le_mask() >> 1));
       over[ovi] = (int32_t)xk;
     }
   }
@@ -1623,33 +1588,18 @@ __global__ __launch_bounds__(256) void k_cmp_scan_sums(const int32_t* __restrict
     if (i < n) t += cs_at(agg, aggb, s, i);
   }
   __shared__ int64_t w4[4];
-  t = (int64_t)wave_sum_u64((unsigned long long)t);
-  if ((threadIdx.x & 63) == 0) w4[threadIdx.x >> 6] = t;
-  __syncthreads();
-  if (threadIdx.x == 0) part[s * pstride + blockIdx.x] = w4[0] + w4[1] + w4[2] + w4[3];
+  t = wg_sum<4>(t, w4);
+  if (threadIdx.x == 0) part[s * pstride + blockIdx.x] = t;
 }
 
 // exclusive scan of every sequence's chunk sums (one workgroup; <= 1024 chunks each)
 __global__ __launch_bounds__(1024) void k_cmp_scan_parts(int64_t* __restrict__ part, int64_t pstride, int nseq,
                                                          int64_t nwg, int nb) {
   __shared__ int64_t wsum[16];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   for (int s = 0; s < nseq; ++s) {
-    const int64_t nch = (cs_len(s, nwg, nb) + kScanChunk - 1) / kScanChunk;
-    const int64_t v = threadIdx.x < nch ? part[s * pstride + threadIdx.x] : 0;
-    // 64-bit inclusive wave scan (shuffles)
-    int64_t incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int64_t t = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += t;
-    }
-    if (lane == 63) wsum[wv] = incl;
-    __syncthreads();
-    int64_t before = 0;
-    for (int q = 0; q < wv; ++q) before += wsum[q];
-    if (threadIdx.x < nch) part[s * pstride + threadIdx.x] = before + incl - v;
-    __syncthreads();
+    int64_t* ps = part + s * pstride;
+    wg_scan_chunks<16>((cs_len(s, nwg, nb) + kScanChunk - 1) / kScanChunk, 0, wsum,
+                       [&](int64_t i) { return ps[i]; }, [&](int64_t i, int64_t before, int64_t) { ps[i] = before; });
   }
 }
 
@@ -1674,17 +1624,8 @@ __global__ __launch_bounds__(256) void k_cmp_scan_out(const int32_t* __restrict_
     t += v[k];
   }
   __shared__ int64_t w4[4];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  int64_t incl = t;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int64_t u = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += u;
-  }
-  if (lane == 63) w4[wv] = incl;
-  __syncthreads();
-  int64_t run = part[s * pstride + blockIdx.x] + incl - t;
-  for (int q = 0; q < wv; ++q) run += w4[q];
+  int64_t total;
+  int64_t run = part[s * pstride + blockIdx.x] + wg_scan_excl<4>(t, w4, total);
 #pragma unroll
   for (int k = 0; k < PER; ++k) {
     if (i0 + k < n) out[i0 + k] = run;

@@ -543,3 +543,112 @@ def test_recommend(native, R, F1, M, indexed, dev):
                             torch.from_numpy(bask).to(dev), index=index)
         assert got.dtype == torch.int32
         assert got.cpu().tolist() == [want[i] for i in ids], [names[i] for i in ids]
+
+
+# ---------------------------------------------------------------------------
+# 7. one-workgroup chunked scans (fa_hip.h wg_scan_chunks): k_scan_small, called directly,
+#    and level 0 of the device loop (section 8).  Every chunked scan -- also
+#    k_dl_pieces_scan and k_dlt_scan, whose chunk loop takes a second step only past
+#    262 144 parent rows or a million candidates, too large for an edge test -- is the
+#    same function with another load / store, so its chunk boundaries are walked here.
+# ---------------------------------------------------------------------------
+SCAN_NS = [0, 1, 63, 64, 65, 1023, 1024, 1025, 2048, 3000]
+
+
+@functools.lru_cache(maxsize=None)
+def _scan_input(K, n, big):
+    rng = np.random.default_rng(700 + 10 * n + K + (5 if big else 0))
+    v = rng.integers(0, 1001, (n, K)).astype(np.int64)
+    if big:
+        # The kernel scans 64 consecutive counts of a sequence in int32 (one wave) and
+        # carries int64 from there on, so the values near 2^30 sit one per 64 elements, at
+        # a random place each: 2^30 + 63 * 1000 < 2^31, and the 47 of them pass 2^32.
+        for k in range(K):
+            at = np.arange(0, n, 64) + rng.integers(0, 64, (n + 63) // 64)
+            at = at[at < n]
+            v[at, k] = (1 << 30) - rng.integers(0, 1000, at.size)
+        assert v.sum(0).min() > 1 << 32
+    return v.astype(np.int32)
+
+
+def _scan_small_check(K, n, big, with_base):
+    v = _scan_input(K, n, big)
+    base = np.array([(7 << 33) + 11, 5][:K], np.int64) if with_base else np.zeros(K, np.int64)
+    want = np.concatenate([base[None], base + np.cumsum(v.astype(np.int64), 0)])     # [n + 1, K]
+    src = torch.from_numpy(v.reshape(-1)).to(DEV) if n else torch.zeros(1, dtype=torch.int32, device=DEV)
+    out = torch.full((K * (n + 1),), -1, dtype=torch.int64, device=DEV)
+    cursor = torch.from_numpy(base).to(DEV) if with_base else None     # the base in, the total out
+    rc = ops._native.hip().fa_hip_scan_small(K, src.data_ptr(), n, out.data_ptr(), prim._p(cursor),
+                                             torch.cuda.current_stream(DEV).cuda_stream)
+    assert rc == 0
+    assert np.array_equal(out.cpu().numpy().reshape(n + 1, K), want)
+    if with_base:
+        assert np.array_equal(cursor.cpu().numpy(), want[n])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("with_base", [False, True], ids=["nobase", "base"])
+@pytest.mark.parametrize("n", SCAN_NS)
+@pytest.mark.parametrize("K", [1, 2])
+def test_scan_small(K, n, with_base):
+    _scan_small_check(K, n, False, with_base)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("with_base", [False, True], ids=["nobase", "base"])
+@pytest.mark.parametrize("K", [1, 2])
+def test_scan_small_int64_carry(K, with_base):
+    _scan_small_check(K, 3000, True, with_base)
+
+
+# ---------------------------------------------------------------------------
+# 8. level 0 of the device loop, nothing past it (max_levels = 1): k_dl_decide0 up to
+#    4 * kDsBlk = 16384 parent rows (by n_bound), k_ds_blocks / k_ds_decide0 / k_ds_add
+#    in 4096-row blocks past it.  The reference is the host generator on the same rows.
+# ---------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _level0_case(n):
+    """F_2-shaped parent rows: the pairs (i, j), i < j <= i + 6, a seeded ~20 % of them
+    removed, the first n in lexicographic order.  Rows have 0..5 candidates, many none.
+    Returns (rows int32 [n, 2], F1, candidates per row int64 [n], candidate rows [C, 3])."""
+    rng = np.random.default_rng(800 + n)
+    items = n // 4 + 8                               # 6 * 0.8 pairs per item: enough for n
+    i = np.repeat(np.arange(items), 6)
+    rows = np.stack([i, i + np.tile(np.arange(1, 7), items)], 1)[rng.random(i.size) >= 0.2][:n]
+    rows = np.ascontiguousarray(rows, np.int32)
+    assert rows.shape == (n, 2)
+    F1 = int(rows.max()) + 1
+    assert F1 < 32768
+    prefix, ext_off, ext = ops.host.apriori_gen(rows)
+    per = np.diff(ext_off)
+    cnt = np.zeros(n, np.int64)
+    cnt[prefix] = per
+    cand = np.concatenate([np.repeat(rows[prefix], per, 0), ext[:, None]], 1).astype(np.int32).reshape(-1, 3)
+    assert cnt.max(initial=0) <= 5 and len(cand) < 4 * n + 4
+    return rows, F1, cnt, cand
+
+
+LEVEL0_CASES = [(n, n, False) for n in (3, 1023, 1024, 1025, 2049)] + \
+               [(n, 16385, True) for n in (3, 4095, 4096, 4097, 8193, 16385)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,n_bound,from_device", LEVEL0_CASES)
+def test_dl_level0(dl_state, n, n_bound, from_device):
+    rows, F1, cnt, cand = _level0_case(n)
+    if n > 1000:
+        assert (cnt == 0).mean() > 0.1 and set(range(5)) <= set(cnt.tolist())
+    S, K, C = dl_state, prim.dl(), len(cand)
+    P0 = torch.from_numpy(rows).to(DEV)
+    n_dev = torch.tensor([n], dtype=torch.int64, device=DEV) if from_device else None
+    c = prim.dl_bundle_gen(S, P0.data_ptr(), prim._p(n_dev), 0 if from_device else n, n_bound, 2, F1, C + 1,
+                           prim.dl_lds_budget(F1), 2.0, 1, torch.cuda.current_stream(DEV).cuda_stream)
+    assert not c[K.kDlOverBound]
+    assert c[K.kDlNl] == n and c[K.kDlCl] == C
+    assert c[K.kDlGl] == int((cnt > 0).sum())
+    ws = S.ws.data_ptr()
+    off = S.ws[int(S.info[2]) - ws:][:8 * (n + 1)].view(torch.int64).cpu().numpy()
+    assert np.array_equal(off, np.concatenate([[0], np.cumsum(cnt)]))
+    got = S.ws[int(S.info[3]) - ws:][:12 * C].view(torch.int32).cpu().numpy().reshape(C, 3)
+    assert np.array_equal(got, cand)
+    del P0
