@@ -1,6 +1,7 @@
-"""Rule building on the host (C++) vs the device (HIP) for a mined result.
+"""Rule building on the host (C++) vs the device (HIP) for a mined result, then the
+recommendation kernels on its rule table (--top-n N: the ranked top-N kernels, too).
 
-    python benchmarks/rules_probe.py [--config T10I4D10M]
+    python benchmarks/rules_probe.py [--config T10I4D10M] [--top-n 10]
 """
 import argparse
 import json
@@ -24,6 +25,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="T10I4D10M")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--top-n", type=int, default=0, help="also time recommend_topn_shard for N = 1 and this N")
     a = ap.parse_args()
     n, L, I, P, N, ms = bench.CONFIGS[a.config]
     dev = torch.device("cuda", 0)
@@ -60,6 +62,29 @@ def main():
     out["users"] = users.n_lines
     out["recommend_agree"] = bool(torch.equal(recs["recommend_indexed"], recs["recommend_scan"]))
     out["users_with_rec"] = int((recs["recommend_indexed"] >= 0).sum())
+    out["distinct_baskets"] = ar.stats.get("distinct_baskets")
+    if a.top_n:
+        # ranked lists on the same rule table and users: N = 1 (the first-match walk with a
+        # one-entry buffer) and N = --top-n, both kernels
+        cons = torch.from_numpy(np.asarray(ar.rules().cons))
+        tops = {}
+        for N in dict.fromkeys((1, a.top_n)):
+            for name, idx in (("indexed", True), ("scan", False)):
+                ar.use_index = idx
+                best = 1e9
+                for _ in range(a.reps):
+                    torch.cuda.synchronize()
+                    t = time.perf_counter()
+                    r = ar.recommend_topn_shard(users, N)
+                    torch.cuda.synchronize()
+                    best = min(best, time.perf_counter() - t)
+                out[f"topn{N}_{name}_ms"] = round(best * 1e3, 2)
+                tops[N, name] = r.cpu()
+            out[f"topn{N}_agree"] = bool(torch.equal(tops[N, "indexed"], tops[N, "scan"]))
+            out[f"topn{N}_entries"] = int((tops[N, "indexed"] >= 0).sum())
+        col0 = tops[1, "indexed"][:, 0].to(torch.int64)
+        first = torch.where(col0 >= 0, cons[col0.clamp(min=0)], torch.full_like(cons[:1], -1))
+        out["topn1_is_first_match"] = bool(torch.equal(first, recs["recommend_indexed"]))
     print(json.dumps(out), flush=True)
 
 

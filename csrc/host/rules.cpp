@@ -200,3 +200,37 @@ FA_API void fa_recommend_cpu(const int64_t* ante_off, const int32_t* ante, const
     }
   });
 }
+
+// Ranked top-n on the CPU (an extension; the reference stops at the first match): the
+// first n firing rules, in table order, whose consequents are pairwise distinct.
+// out[u * n + j] = rule id of entry j, -1 past the last one.  1 <= n; R < 2^31.
+FA_API void fa_recommend_topn_cpu(const int64_t* ante_off, const int32_t* ante, const int32_t* cons,
+                                  int64_t R, int32_t F1, const int64_t* bask_off, const int32_t* bask,
+                                  int64_t M, int32_t n, int32_t* out, int nthreads) {
+  const int64_t words = ((int64_t)F1 + 63) / 64;
+  parallel_for(M, nthreads, 256, [&](int64_t b, int64_t e, int) {
+    std::vector<uint64_t> bits((size_t)std::max<int64_t>(1, words), 0), taken(bits.size(), 0);
+    for (int64_t u = b; u < e; ++u) {
+      const int64_t s = bask_off[u], t = bask_off[u + 1];
+      for (int64_t i = s; i < t; ++i) bits[bask[i] >> 6] |= 1ull << (bask[i] & 63);
+      const int64_t usz = t - s;
+      int32_t* o = out + u * n;
+      int32_t cnt = 0;
+      for (int64_t r = 0; r < R && usz > 0 && cnt < n; ++r) {
+        int32_t c = cons[r];
+        if (((bits[c >> 6] | taken[c >> 6]) >> (c & 63)) & 1) continue;
+        const int64_t a0 = ante_off[r], a1 = ante_off[r + 1];
+        if (a1 - a0 > usz) continue;
+        bool sub = true;
+        for (int64_t i = a0; i < a1; ++i)
+          if (!((bits[ante[i] >> 6] >> (ante[i] & 63)) & 1)) { sub = false; break; }
+        if (!sub) continue;
+        taken[c >> 6] |= 1ull << (c & 63);
+        o[cnt++] = (int32_t)r;
+      }
+      for (int32_t j = 0; j < cnt; ++j) taken[cons[o[j]] >> 6] = 0;
+      for (int32_t j = cnt; j < n; ++j) o[j] = -1;
+      for (int64_t i = s; i < t; ++i) bits[bask[i] >> 6] = 0;
+    }
+  });
+}

@@ -82,6 +82,8 @@ class JobConfig:
     strategy: str = "count"                     # count | candidate distribution
     world_size: int = 0                         # 0: whatever torchrun started; N: launch / require N ranks
     tiebreak: str = "string"                    # rank order of equal-count items (utils.jvm.item_tiebreak_key)
+    top_n: int = 0                              # > 0: also write <out>recommendsTopN (ranked lists, 1..64 items)
+    top_n_scores: bool = False                  # ... every entry as token:confidence
     extra: dict = field(default_factory=dict)
 
 
@@ -116,14 +118,25 @@ def build_parser() -> argparse.ArgumentParser:
                    help="order of frequent items with equal counts (it orders the tokens inside an itemset "
                         "line; the reference's Spark order is not reproducible): string = java.lang.String "
                         "order, numeric = integer tokens by value first")
+    p.add_argument("--top-n", type=int, default=0, metavar="N",
+                   help="also write <output>recommendsTopN/: per U.dat line the first N (1..64) firing rules' "
+                        "consequents with distinct items, in rule order, or 0 when none fires")
+    p.add_argument("--top-n-scores", action="store_true",
+                   help="with --top-n: write every entry as token:confidence")
     return p
 
 
 def parse_args(argv=None) -> JobConfig:
-    a = build_parser().parse_args(argv)
+    p = build_parser()
+    a = p.parse_args(argv)
+    if a.top_n != 0 and not 1 <= a.top_n <= 64:
+        p.error(f"--top-n {a.top_n}: N must be in 1..64")
+    if a.top_n_scores and not a.top_n:
+        p.error("--top-n-scores requires --top-n")
     warn_unread_env()
     return JobConfig(input=a.input, output=a.output, temp=a.temp, min_support=a.min_support, device=a.device,
                      dedup=a.dedup, pair_strategy=a.pair_strategy, with_counts=a.with_counts, resume=a.resume,
                      rules_only=a.rules_only, checkpoint=a.checkpoint, overwrite=a.overwrite,
                      profile=a.profile, metrics_path=a.metrics_path, max_level=a.max_level,
-                     strategy=a.strategy, world_size=a.world_size, tiebreak=a.tiebreak)
+                     strategy=a.strategy, world_size=a.world_size, tiebreak=a.tiebreak, top_n=a.top_n,
+                     top_n_scores=a.top_n_scores)

@@ -157,6 +157,25 @@ def recommend(res: OracleResult, user_lines: list[list[str]]) -> list[str]:
     return out
 
 
+def recommend_topn(res: OracleResult, user_lines: list[list[str]], n: int) -> list[list[tuple[str, float]]]:
+    """Ranked top-n per line (an extension: the reference has no counterpart): the first n
+    firing rules in sorted order whose consequents are pairwise distinct, as (token, conf)."""
+    rules = sort_rules(gen_rules(res), res.items)
+    rank = {t: i for i, t in enumerate(res.items)}
+    out = []
+    for toks in user_lines:
+        u = frozenset(rank[t] for t in toks if t in rank)
+        top, seen = [], set()
+        for a, r, conf in rules:
+            if len(top) == n:
+                break
+            if r not in u and r not in seen and a <= u:
+                seen.add(r)
+                top.append((res.items[r], conf))
+        out.append(top)
+    return out
+
+
 def freq_itemset_lines(res: OracleResult) -> list[str]:
     """``Utils.saveFreqItemset``: tokens rank-descending, lines in Java String order."""
     lines = [" ".join(res.items[r] for r in sorted(s, reverse=True)) for s in res.itemsets]

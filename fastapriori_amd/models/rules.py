@@ -17,6 +17,8 @@ Reference: AssociationRules.scala (class AssociationRules, :17-190).
                                                      tables scan only the per-item rule lists of the
                                                      basket's items (k_recommend_indexed)
   collect to driver + saveRecommends                 gather of rank ids to rank 0
+  (none: the scan stops at the first match)          ranked top-N lists with confidences (run_topn):
+                                                     HIP k_recommend_topn / k_recommend_topn_indexed
 
 Divergences (documented): when there are no rules at all the reference throws
 on ``rules.keys.min`` (:147); we recommend "0" for every user.  Non-integer
@@ -101,21 +103,19 @@ class AssociationRules:
             lut[:vocab.size][hit] = ro[pos[hit]].astype(np.int32)
         return lut
 
-    def recommend_shard(self, users: TransactionShard) -> torch.Tensor:
-        """Recommended rank per local U.dat line (-1 = "0"), on the users' device.
-
-        Identical baskets are recommended once (removeRedundancy's reduceByKey of the
-        rank sets, AssociationRules.scala:51-58): baskets are canonicalised (ranks
-        sorted), grouped by a 128-bit row hash, every group is verified equal to its
-        representative element by element, and the representatives' results fan out
-        to all lines of their group.  Cost O(distinct baskets) instead of O(lines) in
-        the first-match scan."""
+    def _prepare_baskets(self, users: TransactionShard):
+        """What a recommendation kernel needs for a (non-empty) user shard: (rule tensors
+        on the users' device, per-item rule lists or None, F1, CSR of the baskets to
+        scan, fan-out).  Identical baskets are scanned once (removeRedundancy's
+        reduceByKey of the rank sets, AssociationRules.scala:51-58): baskets are
+        canonicalised (ranks sorted), grouped by a 128-bit row hash, every group is
+        verified equal to its representative element by element, and the CSR holds the
+        representatives only; ``inv`` then maps every line to its representative's row
+        (None: the CSR holds every line)."""
         rt = self.rules()
         dev = users.items.device
         lut = torch.from_numpy(self._rank_lut(users.vocab)).to(dev)
         n = users.n_lines
-        if n == 0:
-            return torch.zeros(0, dtype=torch.int32, device=dev)
         F1 = len(self.result.items)
         r = lut[users.items.to(torch.int64)] if users.items.numel() else users.items
         keep = r >= 0
@@ -140,7 +140,7 @@ class AssociationRules:
         groups = self._basket_groups(boff, bask, bcnt) if (self.dedup_baskets and n > 1) else None
         if groups is None:
             self.stats["distinct_baskets"] = n
-            return ops.recommend(a_off, ante, cons, F1, boff, bask, index=index)
+            return (a_off, ante, cons), index, F1, boff, bask, None
         rep, inv = groups
         self.stats["distinct_baskets"] = int(rep.numel())
         rcnt = bcnt[rep]
@@ -149,8 +149,34 @@ class AssociationRules:
         # gather the representatives' baskets into their own CSR
         pos = torch.repeat_interleave(boff[rep] - roff[:-1], rcnt) + torch.arange(int(roff[-1]), device=dev)
         rbask = bask[pos].contiguous()
-        rec = ops.recommend(a_off, ante, cons, F1, roff, rbask, index=index)
-        return rec[inv]
+        return (a_off, ante, cons), index, F1, roff, rbask, inv
+
+    def recommend_shard(self, users: TransactionShard) -> torch.Tensor:
+        """Recommended rank per local U.dat line (-1 = "0"), on the users' device.
+
+        Identical baskets are recommended once (see _prepare_baskets) and the
+        representatives' results fan out to all lines of their group.  Cost O(distinct
+        baskets) instead of O(lines) in the first-match scan."""
+        self.rules()
+        if users.n_lines == 0:
+            return torch.zeros(0, dtype=torch.int32, device=users.items.device)
+        (a_off, ante, cons), index, F1, boff, bask, inv = self._prepare_baskets(users)
+        rec = ops.recommend(a_off, ante, cons, F1, boff, bask, index=index)
+        return rec if inv is None else rec[inv]
+
+    def recommend_topn_shard(self, users: TransactionShard, n: int) -> torch.Tensor:
+        """Ranked top-n per local U.dat line: int32 [n_lines, n] rule ids (-1 padded) on
+        the users' device, see ops.recommend_topn.  The item of an entry is
+        ``rules().cons[id]``, its confidence ``rules().conf[id]``.  Baskets are
+        de-duplicated and the kernel chosen as in recommend_shard."""
+        if not 1 <= n <= 64:
+            raise ValueError(f"recommend_topn_shard: n = {n} is outside 1..64")
+        self.rules()
+        if users.n_lines == 0:
+            return torch.zeros((0, n), dtype=torch.int32, device=users.items.device)
+        (a_off, ante, cons), index, F1, boff, bask, inv = self._prepare_baskets(users)
+        top = ops.recommend_topn(a_off, ante, cons, F1, boff, bask, n, index=index)
+        return top if inv is None else top[inv]
 
     dedup_baskets = True
 
@@ -200,4 +226,30 @@ class AssociationRules:
         out = []
         for p in parts:
             out.extend("0" if v < 0 else items[v] for v in p.tolist())
+        return out
+
+    def run_topn(self, users: TransactionShard, n: int, scores: bool = False) -> list[str] | None:
+        """Ranked top-n for every U.dat line, in file order, on rank 0 (None elsewhere): the
+        items' tokens in list order joined by one space, "0" for an empty list.  With
+        ``scores`` every entry is ``token:conf``, conf the repr() of the rule's float64
+        confidence (the score is what follows the last ':')."""
+        ops.primitives.reset_fallbacks()
+        top = self.recommend_topn_shard(users, n)
+        if ops.primitives.FALLBACKS:
+            self.stats["fallbacks"] = list(ops.primitives.FALLBACKS)
+            for f in ops.primitives.FALLBACKS:
+                self.log.metric(phase="fallback", what=f, stage="rules")
+        parts = self.comm.gather_varlen(top.reshape(-1))
+        if parts is None:
+            return None
+        rt, items = self.rules(), self.result.items
+        cons, conf = rt.cons.tolist(), rt.conf.tolist()
+        out = []
+        for p in parts:
+            for ids in p.reshape(-1, n).tolist():
+                if scores:
+                    ent = [f"{items[cons[i]]}:{conf[i]!r}" for i in ids if i >= 0]
+                else:
+                    ent = [items[cons[i]] for i in ids if i >= 0]
+                out.append(" ".join(ent) if ent else "0")
         return out

@@ -57,6 +57,7 @@ _HOST_SIGS = {
     "fa_rules_export": (None, [vp, vp, vp, vp, vp, vp]),
     "fa_rules_free": (None, [vp]),
     "fa_recommend_cpu": (None, [vp, vp, vp, i64, i32, vp, vp, i64, vp, C.c_int]),
+    "fa_recommend_topn_cpu": (None, [vp, vp, vp, i64, i32, vp, vp, i64, i32, vp, C.c_int]),
     "fa_write_freq_itemsets": (C.c_int, [cp, vp, vp, i32, vp, vp, vp, C.c_int, C.c_int, C.c_int]),
     "fa_cpu_histogram": (None, [vp, i64, i64, vp, C.c_int]),
     "fa_build_probe_table": (None, [vp, i64, C.c_int, C.c_uint32, vp, vp]),
@@ -128,6 +129,8 @@ _HIP_SIGS = {
     "fa_hip_count_candidates": (C.c_int, [vp, i64, i64, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp]),
     "fa_hip_recommend": (C.c_int, [vp, vp, vp, i64, i32, vp, vp, i64, vp, vp]),
     "fa_hip_recommend_indexed": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, vp, vp, i64, vp, vp]),
+    "fa_hip_recommend_topn": (C.c_int, [vp, vp, vp, i64, i32, vp, vp, i64, i32, vp, vp]),
+    "fa_hip_recommend_topn_indexed": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, vp, vp, i64, i32, vp, vp]),
     "fa_hip_parse_tiles": (i64, [i64]),
     "fa_hip_tparse_tiles": (i64, [i64, i64]),
     "fa_hip_tparse_hist_cap": (C.c_int, []),

@@ -1253,6 +1253,42 @@ def recommend(ante_off, ante, cons, F1: int, boff, bask, index=None) -> torch.Te
     return out
 
 
+def recommend_topn(ante_off, ante, cons, F1: int, boff, bask, n: int, index=None) -> torch.Tensor:
+    """Ranked top-n per basket -> int32 [M, n] rule ids, -1 padded (no counterpart in the
+    reference, which stops at the first match).
+
+    Walking the rule table in its order, a basket's list is the first n firing rules
+    (antecedent inside the basket, consequent outside) with pairwise distinct consequents:
+    the item of an entry is ``cons[id]``, its score ``conf[id]``.  Column 0 is the rule
+    behind ``recommend``.  1 <= n <= 64 (one result slot per lane of the basket's wave);
+    ``index`` as in ``recommend``."""
+    if not 1 <= n <= 64:
+        raise ValueError(f"recommend_topn: n = {n} is outside 1..64")
+    M = boff.numel() - 1
+    R = cons.numel()
+    dev = bask.device
+    out = torch.full((max(M, 0), n), -1, dtype=_I32, device=dev)
+    if M <= 0 or R == 0:
+        return out
+    if bask.is_cuda:
+        if index is not None:
+            rc = _native.hip().fa_hip_recommend_topn_indexed(_p(index[0]), _p(index[1]), _p(ante_off), _p(ante),
+                                                             _p(cons), R, F1, _p(boff), _p(bask), M, n, _p(out),
+                                                             _stream(bask))
+        else:
+            rc = _native.hip().fa_hip_recommend_topn(_p(ante_off), _p(ante), _p(cons), R, F1, _p(boff), _p(bask), M,
+                                                     n, _p(out), _stream(bask))
+        if rc == 2:  # vocabulary too wide for an LDS bitset: host path
+            note_fallback(f"top-n recommendation on the host: F1 = {F1} frequent items exceed the kernel's LDS "
+                          "basket bitset (64 KiB)")
+            return recommend_topn(ante_off.cpu(), ante.cpu(), cons.cpu(), F1, boff.cpu(), bask.cpu(), n).to(dev)
+        _native.check(rc, "fa_hip_recommend_topn")
+        return out
+    _native.host().fa_recommend_topn_cpu(_p(ante_off), _p(ante), _p(cons), R, F1, _p(boff), _p(bask), M, n,
+                                         _p(out), num_threads())
+    return out
+
+
 def rules_build_device(levels: list, counts: list, tie_pos: np.ndarray, dev) -> dict:
     """Association rules on the GPU (csrc/hip/rules.hip; AssociationRules.scala:116-182).
 

@@ -118,6 +118,14 @@ def recommend_window(cfg: JobConfig, comm, log: Logger, result, summary: dict) -
     summary["recommend_steps_ms"] = {k: round(v * 1e3, 1) for k, v in
                                      (("read_U", t1 - t0), ("rules", t2 - t1), ("recommend", t3 - t2),
                                       ("write", t4 - t3))}
+    if cfg.top_n > 0:
+        # ranked lists next to the first-match file (no counterpart in the reference)
+        top = ar.run_topn(users, cfg.top_n, scores=cfg.top_n_scores)
+        if comm.is_root:
+            io.write_lines(top, cfg.output + "recommendsTopN", overwrite=cfg.overwrite)
+            summary.update(top_n=cfg.top_n, n_topn_entries=sum(0 if l == "0" else l.count(" ") + 1 for l in top))
+        comm.barrier()
+        summary["recommend_steps_ms"]["topn"] = round((time.perf_counter() - t4) * 1e3, 1)
     summary["n_rules"] = ar.rules().n_rules
     if recs is not None:                   # rank 0 holds every user's recommendation
         summary.update(n_users=len(recs), n_recommended=sum(1 for r in recs if r != "0"))
