@@ -19,6 +19,7 @@
 
 #include "fa_hip.h"
 #include "../host/fa_dl.h"
+#include "../host/fa_limits.h"
 #include "../host/fa_slab.h"
 
 namespace fa {
@@ -53,7 +54,7 @@ __device__ __forceinline__ int64_t lower_bound_i32(const int32_t* __restrict__ a
 // two-deep register pipeline (row offsets two batches ahead, ranks one ahead)
 // and by the 16 resident waves per CU.  The logical block id is XCD-remapped so
 // the nbp tiles of one chunk run on one XCD and re-read the chunk from its L2.
-constexpr int kPW = 16;                // waves per workgroup (1024 threads)
+// (kPW waves per workgroup: fa_limits.h)
 constexpr int kWSpan = 1024;           // ranks staged per wave batch
 constexpr int kWPer = kWSpan / 64;     // per lane
 
@@ -343,6 +344,7 @@ constexpr int kPB16 = 256;
 constexpr int kRowsDw = 2;                  // staged dwords per lane and block
 constexpr int kRowsStage = 64 * kRowsDw * 4; // 512 staged local-rank bytes per wave and block
 constexpr int kRowsWin = kRowsStage / 64;    // 8 windows
+static_assert(kPairLrPad >= kRowsStage + 3, "lr's pad covers a batch's staged dwords from an aligned-down base");
 
 // Batches [q0, q1) of tile (bi, bj) into the packed-u16 LDS tile (no barriers).
 constexpr int kTriTab = 64 * 63 / 2;
@@ -365,7 +367,7 @@ struct PairRowsLds {
 // still filling would wait for it).  Per batch: "meta" = the rows' block counts
 // and the two segment bases, issued two batches ahead; "bytes" = the segments'
 // aligned dwords (addresses from meta), issued one batch ahead.  Every load is
-// unconditional -- cnt, base and lr are padded past their ends by the launcher
+// unconditional -- cnt, base and lr are padded past their ends by the caller (fa_limits.h)
 // (batches past the chunk read real or padding data that is never processed) --
 // so the compiler's wait counts are exact and a wait never drains the loads
 // issued for later batches.
@@ -402,7 +404,7 @@ __device__ __forceinline__ void pair_rows16_chunk_t(PairRowsLds& L, const uint8_
                        ((int64_t)__builtin_amdgcn_readlane((int)(B.vb >> 32), 0) << 32);
     const uint32_t* pa = reinterpret_cast<const uint32_t*>(lr + (oa & ~(int64_t)3));
 #pragma unroll
-    for (int k = 0; k < kRowsDw; ++k) B.da[k] = pa[lane + 64 * k];   // lr is padded by >= 1 KiB
+    for (int k = 0; k < kRowsDw; ++k) B.da[k] = pa[lane + 64 * k];   // lr is padded by kPairLrPad
     if (!kDiag) {
       const int64_t ob = (int64_t)__builtin_amdgcn_readlane((int)B.vb, 1) |
                          ((int64_t)__builtin_amdgcn_readlane((int)(B.vb >> 32), 1) << 32);
@@ -559,6 +561,7 @@ __device__ __forceinline__ void pair_rows16_chunk_t(PairRowsLds& L, const uint8_
     }
     wave_lds_sync();
   };
+  static_assert(kPairAhead == 3, "three register sets");
   // batch t lives in set t % 3: its meta is issued two batches before its bytes'
   // turn, its bytes one batch before it is processed
   int64_t q = q0 + wv;
@@ -571,15 +574,15 @@ __device__ __forceinline__ void pair_rows16_chunk_t(PairRowsLds& L, const uint8_
   for (;;) {
     load_bytes(Y);
     process(X, q);
-    load_meta(X, q + 3 * kPW);
+    load_meta(X, q + kPairAhead * kPW);
     if ((q += kPW) >= q1) break;
     load_bytes(Z);
     process(Y, q);
-    load_meta(Y, q + 3 * kPW);
+    load_meta(Y, q + kPairAhead * kPW);
     if ((q += kPW) >= q1) break;
     load_bytes(X);
     process(Z, q);
-    load_meta(Z, q + 3 * kPW);
+    load_meta(Z, q + kPairAhead * kPW);
     if ((q += kPW) >= q1) break;
   }
 }
@@ -1185,7 +1188,6 @@ __global__ __launch_bounds__(256) void k_pair_gram_fp4(BmView bm, int32_t F1,
 // extension's words, and the 4 waves reduce into an LDS accumulator.
 // ---------------------------------------------------------------------------
 constexpr int kWPT = 8;
-constexpr int kMaxBlockExt = 1024;
 
 template <bool kWeighted>
 __global__ __launch_bounds__(256) void k_count_candidates(
@@ -1254,8 +1256,6 @@ __global__ __launch_bounds__(256) void k_count_candidates(
 // the global bitmap is never materialised.  One coalesced atomic per candidate
 // per workgroup at the end.
 // ---------------------------------------------------------------------------
-constexpr int kSlabThreads = 1024;
-
 // Slab build modes: per-column rank prefetch (dedup: columns gather rows through
 // src), wave-cooperative coalesced build (columns = rows, contiguous ranks), or
 // a copy from the materialised used-item bitmap (multi-pass levels).
@@ -1848,7 +1848,6 @@ __device__ __forceinline__ uint64_t bm_word(const uint64_t* __restrict__ bm, int
   return ld > 0 ? bm[r * ld + q] : bm[(q >> 3) * -ld + r * 8 + (q & 7)];
 }
 
-constexpr int kWinPlanes = 11;   // counts up to 2047 items
 constexpr int kWinAhead = 8;     // item words loaded ahead (k_win_alive)
 constexpr int kWinBatch = 8;     // items per LDS round (k_win_compact)
 

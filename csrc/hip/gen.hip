@@ -17,6 +17,7 @@
 
 #include "fa_hip.h"
 #include "../host/fa_dl.h"
+#include "../host/fa_limits.h"
 #include "../host/fa_slab.h"
 
 namespace fa {
@@ -212,8 +213,6 @@ __global__ __launch_bounds__(256) void k_ag_rows(const int32_t* __restrict__ P, 
 
 // bitset words per lane for nw words: 1, 2, 4 or 8 (F1 <= 32768)
 static inline int ag_nwl(int nw) { return nw <= 64 ? 1 : nw <= 128 ? 2 : nw <= 256 ? 4 : 8; }
-// u32 words of a chain's used-item bitset (ops.primitives.ag_mark_words mirrors this)
-static inline int ag_mark_words(int F1) { return std::max(128, (F1 + 31) / 32); }
 // LAUNCH(N) for the lane width N of nw bitset words
 #define FA_AG_NWL_SWITCH(nw, LAUNCH) \
   switch (ag_nwl(nw)) {              \
@@ -743,7 +742,6 @@ __global__ __launch_bounds__(1024) void k_dl_decide0(const int32_t* __restrict__
 // (1) kDsBlk-row block scans into off[] (block-local) with the block totals, (2) one
 // workgroup scans the totals and takes k_dl_decide0's decisions, (3) the block bases
 // are added to off[].  bs: int64 scratch [3 * nblk].
-constexpr int kDsBlk = 4096;
 
 __global__ __launch_bounds__(1024) void k_ds_blocks(const int32_t* __restrict__ cnt, int64_t* __restrict__ off,
                                                     const long long* __restrict__ c, int64_t* __restrict__ bs,
@@ -1049,7 +1047,7 @@ static void dl_post(DlPost* P, const DlDesc* desc, int L, long long* ctl, const 
     }
     if (den > 0.0) {
       double est_rows = 0.0, est_nnz = 0.0;
-      trim_estimate(P->len_hist, 256, num / den, (int)P->k, &est_rows, &est_nnz);
+      trim_estimate(P->len_hist, kTrimHist, num / den, (int)P->k, &est_rows, &est_nnz);
       const double T = (double)std::max<int64_t>(P->T, 1), nnz = (double)std::max<int64_t>(P->nnz, 1);
       P->trim = (est_rows < P->trim_rows_frac * T || est_nnz < P->trim_nnz_frac * nnz) ? 1 : 0;
     }

@@ -16,6 +16,7 @@
 //   (numeric ids: the tile parser below; dictionary ids: k_parse_lines_dict, then
 //   k_compact_lines, one thread per line copying ids and extras to their offsets)
 #include "fa_hip.h"
+#include "../host/fa_limits.h"
 
 namespace fa {
 
@@ -132,7 +133,6 @@ constexpr int kTTile = kTT * kTBy;       // = kLTile: k_tline_count uses the sam
 constexpr int kHalo = 2048;
 constexpr int kTLds = kHalo + kTTile + 64;
 constexpr int kSeenT = 16;
-constexpr int kHistCap = 8192;
 
 __global__ __launch_bounds__(kLT) void k_tline_count(const uint8_t* __restrict__ buf, int64_t a, int64_t lo,
                                                      int64_t hi, int32_t* __restrict__ tile_cnt) {
@@ -691,7 +691,6 @@ FA_API int64_t fa_hip_tparse_tiles(int64_t lo, int64_t hi) {
   return hi > lo ? (hi - a + kLTile - 1) / kLTile : 0;
 }
 
-FA_API int fa_hip_tparse_hist_cap() { return kHistCap; }
 
 FA_API int fa_hip_tline_count(const uint8_t* buf, int64_t lo, int64_t hi, int32_t* tile_cnt, hipStream_t st) {
   const int64_t a = lo & ~(int64_t)63;

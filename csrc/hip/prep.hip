@@ -6,6 +6,7 @@
 // :66-70 (compress + size filter), :71-79 (dedup), :195-210 (vertical transpose,
 // done there as F1 separate Spark jobs producing 1 byte per transaction).
 #include "fa_hip.h"
+#include "../host/fa_limits.h"
 
 namespace fa {
 
@@ -13,7 +14,6 @@ namespace fa {
 // Histogram over token ids.  V <= kLdsBins: LDS-privatised per workgroup, one
 // global atomic per non-zero bin per workgroup; otherwise global atomics.
 // ---------------------------------------------------------------------------
-constexpr int kLdsBins = 16384;
 
 // The LDS bins are dynamic: V * nrep words, so a T10-scale vocabulary (V ~ 1000) leaves
 // room for many workgroups per CU (a static 64 KB array allowed two).  nrep = 4 gives each
@@ -61,8 +61,6 @@ __global__ __launch_bounds__(256) void k_histogram(const int32_t* __restrict__ i
 // behind it while the host reads the ranking back.  pack (int64 [2 V + 1]): [0] the
 // number of frequent ids F, [1 .. F] the ids in rank order, [V + 1 .. V + F] their supports.
 // ---------------------------------------------------------------------------
-constexpr int kF1RankMax = 2048;
-
 __device__ __forceinline__ int64_t f1_tie_key(int64_t fid, int numeric) {
   if (numeric) return fid == 0 ? INT64_MAX : fid - 1;
   if (fid == 0) return -16;                       // "" sorts first (key -1, length 0)
@@ -116,11 +114,10 @@ __global__ __launch_bounds__(256) void k_f1_rank(const int64_t* __restrict__ his
 // LDS per workgroup, one workgroup per CU), each workgroup storing its private
 // sketch to partial[wg] (summed by the caller).  Pass 2: exact counts for the
 // sketch's candidates only, through an LDS open-addressing table (keys -1 =
-// empty, linear probing).  Both hashes are multiplicative; the host mirrors
-// them (fastapriori_amd/ops/primitives.py: _sk_hash) to build the table.
+// empty, linear probing).  Both hashes are multiplicative (fa_limits.h kSkA0 / kSkA1);
+// the host builds the table with the first (ops.primitives.f1_exact).
 // ---------------------------------------------------------------------------
-constexpr int kSkLog = 14, kSkW = 1 << kSkLog;
-constexpr uint32_t kSkA0 = 0x9E3779B1u, kSkA1 = 0x85EBCA77u;
+constexpr int kSkW = 1 << kSkLog;
 
 template <bool kVec, class F>
 __device__ __forceinline__ void for_each_item(const int32_t* __restrict__ items, int64_t nnz, F&& f) {
@@ -318,8 +315,6 @@ __global__ __launch_bounds__(256) void k_compress_regs(
 // sorted output span is written back coalesced.  Rows longer than N go to the
 // overflow list; their (garbage) slots in the output span are rewritten by the
 // next tier, which runs later on the same stream.
-constexpr int kCSpan = 8192;
-
 // SPAN = staged input tokens per workgroup (32 KB at N = 16; 64 KB for the
 // 64-token tier of long-ish rows, e.g. T40I10's 40-token transactions, whose
 // 256-row spans do not fit 8192 and would otherwise be gathered row by row).
@@ -404,7 +399,6 @@ __global__ __launch_bounds__(256) void k_compress_staged(
 }
 
 // Long rows: one 256-thread workgroup per row, bitonic sort in LDS (<= 16384).
-constexpr int kLongMax = 16384;
 __global__ __launch_bounds__(256) void k_compress_lds(
     const int64_t* __restrict__ off, const int32_t* __restrict__ items, const int32_t* __restrict__ lut,
     const int32_t* __restrict__ rows, const int32_t* __restrict__ kept, const int64_t* __restrict__ roff,
@@ -448,8 +442,6 @@ __global__ __launch_bounds__(256) void k_compress_lds(
 // sets its bit in a per-wave LDS bitmap (ds_or_b64).  Lane l owns words
 // l + 64m; a popcount + DPP prefix scan over the words gives every lane its
 // output position, so ranks come out ascending.  Lanes clear their own words.
-constexpr int kCwMaxWords = 16;   // words per lane -> F1 <= 16 * 64 * 64
-
 __global__ __launch_bounds__(256) void k_compress_wave(
     const int64_t* __restrict__ off, const int32_t* __restrict__ items, const int32_t* __restrict__ lut,
     const int32_t* __restrict__ rows, int64_t nrows, const int32_t* __restrict__ kept,
@@ -533,8 +525,6 @@ __global__ __launch_bounds__(256) void k_row_hash(const int64_t* __restrict__ ro
 // the marked bits estimate the distinct rows by linear counting.  T is read from
 // device memory (the compression scan's total), so the probe is queued behind the
 // emit pass and its result travels with the compression sizes in one readback.
-constexpr int kProbeBits = 1 << 22;
-
 // Only rows of <= kCmpProbeLen items are hashed (the emit pass has written them; longer
 // rows are finished by later tiers); hashed counts them.
 constexpr int kCmpProbeLen = 16;
@@ -695,8 +685,6 @@ __device__ __forceinline__ unsigned long long lane_range(int lo, int hi) {   // 
   return hi > lo ? (h & ~l) : 0ull;
 }
 
-constexpr int kTrimAliveLds = 32768;
-
 struct TrimWave {
   int64_t base;   // first rank position of the wave's rows
   int n;          // ranks in the wave's rows
@@ -757,8 +745,6 @@ __global__ __launch_bounds__(256) void k_trim_scan_count(const int64_t* __restri
   __syncthreads();
   if (threadIdx.x == 0) { bk_rows[blockIdx.x] = tr; bk_nnz[blockIdx.x] = tn; }
 }
-
-constexpr int kTrimHist = 256;
 
 template <bool kLdsAlive>
 __global__ __launch_bounds__(256) void k_trim_emit(const int64_t* __restrict__ roff, const int32_t* __restrict__ ranks,
@@ -824,10 +810,10 @@ __global__ __launch_bounds__(256) void k_trim_emit(const int64_t* __restrict__ r
     }
   }
   __syncthreads();
-  // 64 striped copies (summed by the caller): one shared copy would serialise
+  // kTrimStripes striped copies (summed by the caller): one shared copy would serialise
   // ~10 bins x every block on a few L2 lines
   if (hist && hs[threadIdx.x])
-    atomicAdd((unsigned long long*)&hist[(blockIdx.x & 63) * kTrimHist + threadIdx.x], (unsigned long long)hs[threadIdx.x]);
+    atomicAdd((unsigned long long*)&hist[(blockIdx.x & (kTrimStripes - 1)) * kTrimHist + threadIdx.x], (unsigned long long)hs[threadIdx.x]);
 }
 
 
@@ -849,7 +835,6 @@ __global__ __launch_bounds__(256) void k_trim_emit(const int64_t* __restrict__ r
 // 16 KB spans (4096 tokens per 256 rows: every T10I4 workgroup) keep 8
 // workgroups resident per CU, which hides the dependent offset -> token -> LUT
 // loads of these short-lived workgroups.
-constexpr int kCmpSpan = 4096;
 constexpr int kCmpPer = kCmpSpan / 256;
 __device__ __forceinline__ bool cmp_stage(uint32_t* buf, const int32_t* __restrict__ items,
                                           const int32_t* __restrict__ lut, int64_t base, int64_t n_in) {
@@ -874,7 +859,6 @@ __device__ __forceinline__ bool cmp_stage(uint32_t* buf, const int32_t* __restri
 }
 
 constexpr int kCmpN = 16;          // rows of <= kCmpN tokens are sorted by k_cmp_emit
-constexpr int kCmpStripes = 64;    // histogram copies
 // Rows of kCmpN < L <= kCmpMid tokens in a staged span are sorted by k_cmp_emit too,
 // with wave-wide bitonic networks on the span already in LDS (rows of <= 32 tokens
 // two per network, one per 32-lane half) -- at most kCmpMidPerWave per wave, the
@@ -882,7 +866,6 @@ constexpr int kCmpStripes = 64;    // histogram copies
 // k_compress_regs<64>, gathers every such row again from HBM: 1.6-1.7 ms per
 // T10I4D100M run.)
 constexpr int kCmpMid = 64;
-constexpr int kCmpMidPerWave = 8;
 
 // the same rows in k_cmp_agg and k_cmp_emit (their overflow counts must agree)
 __device__ __forceinline__ bool cmp_mid(bool kept, int64_t L, bool staged) {
@@ -926,10 +909,10 @@ __device__ __forceinline__ unsigned long long blk_inc(uint32_t v) {
 
 // per-workgroup totals of the rows' block counts: aggb[b * gridDim.x + workgroup]
 __device__ __forceinline__ void cmp_block_totals(unsigned long long pc, int nb, int32_t* __restrict__ aggb) {
-  __shared__ int bs[8][4];
+  __shared__ int bs[kCmpMaxNB][4];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
-  for (int b = 0; b < 8; ++b) {
+  for (int b = 0; b < kCmpMaxNB; ++b) {
     if (b >= nb) break;
     const int t = wave_last(wave_scan_incl_dpp((int)((pc >> (8 * b)) & 255)));
     if (lane == 0) bs[b][w] = t;
@@ -945,7 +928,7 @@ __global__ __launch_bounds__(256) void k_cmp_agg(const int64_t* __restrict__ off
                                                  int32_t* __restrict__ agg, uint32_t* __restrict__ hist,
                                                  int32_t* __restrict__ aggb, int nb) {
   __shared__ uint32_t buf[kCmpSpan];
-  __shared__ uint32_t lh[256];
+  __shared__ uint32_t lh[kCmpHist];
   __shared__ int sh[8];
   const int64_t r0 = (int64_t)blockIdx.x * 256, r1 = min(n, r0 + 256);
   const int64_t r = r0 + threadIdx.x;
@@ -966,7 +949,7 @@ __global__ __launch_bounds__(256) void k_cmp_agg(const int64_t* __restrict__ off
   const int kc[2] = {kept, kept ? c : 0};        // kept rows, their items
   int ex[2], tot[2];
   wg_scan_excl<4>(kc, sh, ex, tot);
-  if (kept) atomicAdd(&lh[min(c, 255)], 1u);
+  if (kept) atomicAdd(&lh[min(c, kCmpHist - 1)], 1u);
   const bool mid = cmp_mid(kept, e - s, staged);
   const unsigned long long ob = __ballot(kept && e - s > kCmpN && !mid);
   __shared__ int ov_w[4];
@@ -979,7 +962,7 @@ __global__ __launch_bounds__(256) void k_cmp_agg(const int64_t* __restrict__ off
   }
   // striped histogram copies: 390K workgroups adding into one 256-bin row would
   // serialise on a few hot addresses (~10 distinct row lengths)
-  if (lh[threadIdx.x]) atomicAdd(&hist[(blockIdx.x & (kCmpStripes - 1)) * 256 + threadIdx.x], lh[threadIdx.x]);
+  if (lh[threadIdx.x]) atomicAdd(&hist[(blockIdx.x & (kCmpStripes - 1)) * kCmpHist + threadIdx.x], lh[threadIdx.x]);
 }
 
 __global__ __launch_bounds__(256) void k_cmp_emit(const int64_t* __restrict__ off, const int32_t* __restrict__ items,
@@ -999,7 +982,7 @@ __global__ __launch_bounds__(256) void k_cmp_emit(const int64_t* __restrict__ of
   // fused pair layout (lr != null): row x's block-b segment start in the workgroup's
   // block-b span minus the row's first block-b index, tabx[x * nb + b]
   extern __shared__ int32_t tabx[];
-  __shared__ int64_t wgb[8];
+  __shared__ int64_t wgb[kCmpMaxNB];
   const bool blk = bcnt != nullptr;
   const int64_t r0 = (int64_t)blockIdx.x * 256, r1 = min(n, r0 + 256);
   const int64_t r = r0 + threadIdx.x;
@@ -1066,11 +1049,11 @@ __global__ __launch_bounds__(256) void k_cmp_emit(const int64_t* __restrict__ of
     const int64_t bld = pre_rows[gridDim.x];
     const unsigned long long pk = kept ? pc : 0ull;
     const unsigned long long fpre = (pk << 8) * 0x0101010101010101ull;   // byte b: items in blocks < b
-    __shared__ int bs2[8][4];
+    __shared__ int bs2[kCmpMaxNB][4];
     const int lane_ = threadIdx.x & 63;
-    int exb[8];
+    int exb[kCmpMaxNB];
 #pragma unroll
-    for (int b = 0; b < 8; ++b) {
+    for (int b = 0; b < kCmpMaxNB; ++b) {
       exb[b] = 0;
       if (b < nb) {
         const int cb = (int)((pk >> (8 * b)) & 255);
@@ -1082,7 +1065,7 @@ __global__ __launch_bounds__(256) void k_cmp_emit(const int64_t* __restrict__ of
     if (lr && (int)threadIdx.x < nb) wgb[threadIdx.x] = preb[(int64_t)threadIdx.x * gridDim.x + blockIdx.x];
     __syncthreads();
 #pragma unroll
-    for (int b = 0; b < 8; ++b) {
+    for (int b = 0; b < kCmpMaxNB; ++b) {
       if (b < nb) {
         for (int k = 0; k < w; ++k) exb[b] += bs2[b][k];
         if (kept) bcnt[(int64_t)b * bld + xk] = (uint8_t)(pk >> (8 * b));
@@ -1195,14 +1178,14 @@ __global__ __launch_bounds__(256) void k_block_counts_rows(const int64_t* __rest
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nrows || (flags && !flags[i])) return;
   const int64_t x = rows[i];
-  int c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int c[kCmpMaxNB] = {};
   for (int64_t k = roff[x], e = roff[x + 1]; k < e; ++k) {
     const int b = ranks[k] >> 8;
 #pragma unroll
-    for (int q = 0; q < 8; ++q) c[q] += b == q;
+    for (int q = 0; q < kCmpMaxNB; ++q) c[q] += b == q;
   }
 #pragma unroll
-  for (int q = 0; q < 8; ++q)
+  for (int q = 0; q < kCmpMaxNB; ++q)
     if (q < nb) bcnt[(int64_t)q * bld + x] = (uint8_t)min(c[q], 255);
 }
 
@@ -1247,7 +1230,7 @@ using namespace fa;
 FA_API int fa_hip_block_counts_rows(const int64_t* roff, const int32_t* ranks, const int32_t* rows, int64_t nrows,
                                     uint8_t* bcnt, int64_t bld, int nb, const int8_t* flags, hipStream_t st) {
   if (nrows <= 0) return 0;
-  if (nb > 8) return 1;
+  if (nb > kCmpMaxNB) return 1;
   hipLaunchKernelGGL(k_block_counts_rows, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, st, roff, ranks, rows,
                      nrows, bcnt, bld, nb, flags);
   FA_LAUNCH_RET();
@@ -1313,10 +1296,10 @@ __global__ __launch_bounds__(256) void k_txn_freq_count_wave(const int64_t* __re
 }
 
 static int f1_grid(int64_t nnz) {
-  return (int)std::max<int64_t>(1, std::min<int64_t>(256, (nnz + 1024 * 64 - 1) / (1024 * 64)));
+  return (int)std::max<int64_t>(1, std::min<int64_t>(kSkGridMax, (nnz + 1024 * 64 - 1) / (1024 * 64)));
 }
 
-// partial: [f1_grid(nnz)][2 * 16384] u32; returns the number of partial sketches via *nwg.
+// partial: [f1_grid(nnz) <= kSkGridMax][2 << kSkLog] u32; returns the number of partial sketches via *nwg.
 FA_API int fa_hip_f1_sketch(const int32_t* items, int64_t nnz, uint32_t* partial, int* nwg, hipStream_t st) {
   const int g = f1_grid(nnz);
   *nwg = g;
@@ -1428,7 +1411,7 @@ FA_API int fa_hip_compress_regs_bc(const int64_t* off, const int32_t* items, con
                                    int64_t nrows, const int32_t* kept, const int64_t* roff, int32_t* ranks,
                                    int8_t* over_flag, uint8_t* bcnt, int64_t bld, int nb, hipStream_t st) {
   if (nrows <= 0) return 0;
-  if (nb < 1 || nb > 8) return 1;
+  if (nb < 1 || nb > kCmpMaxNB) return 1;
   hipLaunchKernelGGL(k_compress_regs<64>, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, st, off, items, lut,
                      rows, nrows, kept, roff, ranks, over_flag, bcnt, bld, nb);
   FA_LAUNCH_RET();
@@ -1469,14 +1452,14 @@ FA_API int fa_hip_compress_lds(const int64_t* off, const int32_t* items, const i
   FA_LAUNCH_RET();
 }
 
-// rows == nullptr: kept rows 0..nrows-1.  Requires F1 <= 65536.
+// rows == nullptr: kept rows 0..nrows-1.  Requires F1 <= kCwMaxF1.
 // flags (optional): int8 [nrows], only rows with a non-zero flag are compressed
 FA_API int fa_hip_compress_wave(const int64_t* off, const int32_t* items, const int32_t* lut, const int32_t* rows,
                                 int64_t nrows, const int32_t* kept, const int64_t* roff, int32_t* ranks, int F1,
                                 const int8_t* flags, hipStream_t st) {
   if (nrows <= 0) return 0;
   const int M = (F1 + 4095) / 4096;
-  if (M > kCwMaxWords) return 1;
+  if (F1 > kCwMaxF1) return 1;
   const int64_t g = std::min<int64_t>((nrows + 3) / 4, 8192);
   hipLaunchKernelGGL(k_compress_wave, dim3((unsigned)g), dim3(256), 0, st, off, items, lut, rows, nrows, kept, roff,
                      ranks, std::max(M, 1), flags);
@@ -1495,7 +1478,7 @@ FA_API int fa_hip_row_hash(const int64_t* roff, const int32_t* ranks, int64_t T,
 FA_API int fa_hip_dedup_probe(const int64_t* roff, const int32_t* ranks, const int64_t* T_dev, int64_t n_max,
                               uint32_t* ws, unsigned long long* tail, hipStream_t st) {
   if (n_max <= 0) return 0;
-  if (n_max > (int64_t)1 << 24) return 1;
+  if (n_max > kProbeMaxRows) return 1;
   const int nparts = (int)((n_max + 255) / 256);
   uint32_t* part = ws + n_max;
   hipLaunchKernelGGL(k_dedup_probe, dim3((unsigned)nparts), dim3(256), 0, st, roff, ranks, T_dev, n_max, ws, part);
@@ -1540,7 +1523,7 @@ FA_API int fa_hip_trim_scan_count(const int64_t* roff, const int32_t* ranks, int
   FA_LAUNCH_RET();
 }
 
-// hist: int64 [64][256] striped row-length histogram (length clamped to 255) or nullptr.
+// hist: int64 [kTrimStripes][kTrimHist] striped row-length histogram (length clamped to the last bin) or nullptr.
 FA_API int fa_hip_trim_emit(const int64_t* roff, const int32_t* ranks, const int8_t* alive, int F1, int64_t T,
                             const int32_t* cnt, const int64_t* base_rows, const int64_t* base_nnz, int64_t* nroff,
                             int32_t* nranks, int32_t* kept, int64_t* hist, hipStream_t st) {
@@ -1555,8 +1538,8 @@ FA_API int fa_hip_trim_emit(const int64_t* roff, const int32_t* ranks, const int
   FA_LAUNCH_RET();
 }
 
-// Two-pass fused compression: agg int32 [3 * nwg], hist u32 [64 * 256] striped copies (zeroed by the caller).
-// aggb (optional, nb <= 8 256-rank blocks): int32 [nb * nwg] per-workgroup block totals
+// Two-pass fused compression: agg int32 [3 * nwg], hist u32 [kCmpStripes][kCmpHist] striped copies (zeroed by the caller).
+// aggb (optional, nb <= kCmpMaxNB 256-rank blocks): int32 [nb * nwg] per-workgroup block totals
 // (the fused pair layout of k_cmp_emit).
 // ---------------------------------------------------------------------------
 // Exclusive scans of k_cmp_agg's per-workgroup aggregates for k_cmp_emit, in three
@@ -1567,8 +1550,6 @@ FA_API int fa_hip_trim_emit(const int64_t* roff, const int32_t* ranks, const int
 // s = 3 (aggb != null) the block-major block totals, nb * nwg -> preb[0 .. nb * nwg].
 // Also roff[0] = 0.
 // ---------------------------------------------------------------------------
-constexpr int kScanChunk = 4096;      // elements per workgroup (256 threads x 16)
-
 __device__ __forceinline__ int64_t cs_len(int s, int64_t nwg, int nb) { return s < 3 ? nwg : nb * nwg; }
 __device__ __forceinline__ int32_t cs_at(const int32_t* __restrict__ agg, const int32_t* __restrict__ aggb, int s,
                                          int64_t i) {
@@ -1651,13 +1632,13 @@ FA_API int fa_hip_cmp_scan(const int32_t* agg, const int32_t* aggb, int64_t nwg,
 FA_API int fa_hip_cmp_agg(const int64_t* off, const int32_t* items, const int32_t* lut, int64_t n, int32_t* agg,
                           uint32_t* hist, int32_t* aggb, int nb, hipStream_t st) {
   if (n <= 0) return 0;
-  if (aggb && (nb < 1 || nb > 8)) return 1;
+  if (aggb && (nb < 1 || nb > kCmpMaxNB)) return 1;
   hipLaunchKernelGGL(k_cmp_agg, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, off, items, lut, n, agg, hist,
                      aggb, nb);
   FA_LAUNCH_RET();
 }
 
-// bcnt (optional, nb <= 8): u8 [nb * T] per-row block counts.  lr (optional, needs bcnt
+// bcnt (optional, nb <= kCmpMaxNB): u8 [nb * T] per-row block counts.  lr (optional, needs bcnt
 // and preb = the exclusive scan of fa_hip_cmp_agg's aggb, nb * nwg + 1 entries): the
 // pair kernel's blocked local-rank layout, u8 [lr_cap]; lbase: int64 [nb * ceil(T / 64)]
 // batch bases (zeroed padding past it is the caller's); ovb: int64 [rows * nb] the
@@ -1667,7 +1648,7 @@ FA_API int fa_hip_cmp_emit(const int64_t* off, const int32_t* items, const int32
                            int64_t* roff, int32_t* ranks, int32_t* over, uint8_t* bcnt, int nb, const int64_t* preb,
                            uint8_t* lr, int64_t lr_cap, int64_t* lbase, int64_t* ovb, hipStream_t st) {
   if (n <= 0) return 0;
-  if (bcnt && (nb < 1 || nb > 8)) return 1;
+  if (bcnt && (nb < 1 || nb > kCmpMaxNB)) return 1;
   if (lr && (!bcnt || !preb || !lbase || !ovb)) return 1;
   const size_t dyn = lr ? (size_t)256 * nb * sizeof(int32_t) : 0;
   hipLaunchKernelGGL(k_cmp_emit, dim3((unsigned)((n + 255) / 256)), dim3(256), dyn, st, off, items, lut, n, pre_rows,

@@ -1,10 +1,11 @@
-// fa_dl.h by name, for fastapriori_amd.ops.primitives (ctypes): Python reads the device
-// loop's slots, limits and mode bits, DlDesc's fields and DlPost's layout from here and
-// keeps no copy of them.
+// fa_dl.h and fa_limits.h by name, for fastapriori_amd.ops.primitives (ctypes): Python
+// reads the device loop's slots, limits and mode bits, DlDesc's fields and DlPost's
+// layout, and the kernels' capacity limits and pads from here and keeps no copy of them.
 #include <stddef.h>
 
 #include "fa_common.h"
 #include "fa_dl.h"
+#include "fa_limits.h"
 
 namespace {
 
@@ -39,11 +40,21 @@ static_assert(sizeof(DlDesc) == 8 * (0 FA_DL_DESC_FIELDS(FA_DL_X)), "FA_DL_DESC_
 static_assert(sizeof(DlPost) == 8 * (0 FA_DL_POST_FIELDS(FA_DL_X)), "FA_DL_POST_FIELDS lists every field");
 #undef FA_DL_X
 
+const Entry kLimits[] = {
+#define FA_LIMITS_X(name, value) {#name, value},
+    FA_LIMITS_INT(FA_LIMITS_X) FA_LIMITS_U32(FA_LIMITS_X)
+#undef FA_LIMITS_X
+};
+
+template <int N>
+const char* entry(const Entry (&table)[N], int i, int64_t* value) {
+  if (i < 0 || i >= N) return nullptr;
+  *value = table[i].value;
+  return table[i].name;
+}
+
 }  // namespace
 
-// Entry i of the table: its name (nullptr past the end) and, in *value, its value
-FA_API const char* fa_dl_layout(int i, int64_t* value) {
-  if (i < 0 || i >= (int)(sizeof(kLayout) / sizeof(kLayout[0]))) return nullptr;
-  *value = kLayout[i].value;
-  return kLayout[i].name;
-}
+// Entry i of a table: its name (nullptr past the end) and, in *value, its value
+FA_API const char* fa_dl_layout(int i, int64_t* value) { return entry(kLayout, i, value); }
+FA_API const char* fa_limits(int i, int64_t* value) { return entry(kLimits, i, value); }

@@ -95,7 +95,7 @@ struct DlPost {
   const int64_t* roff; const int32_t* ranks; const int32_t* src; const int32_t* wword;
   int64_t ncols; double lds_kernel; double lds_budget;
   // trimming decision (trim_ok = 0: never): c1 int64 [F1] item supports, alive uint8 [F1],
-  // len_hist int64 [256] (nullptr: decided by the caller), T rows, nnz, min rows, level k
+  // len_hist int64 [kTrimHist] (fa_limits.h; nullptr: decided by the caller), T rows, nnz, min rows, level k
   const int64_t* c1; const uint8_t* alive; const int64_t* len_hist;
   int64_t T, nnz, trim_min_rows, trim_ok, k;
   // out

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "fa_common.h"
+#include "fa_limits.h"
 #include "fa_slab.h"
 
 using namespace fa;
@@ -69,12 +70,11 @@ FA_API void fa_trim_estimate(const int64_t* len_hist, int64_t n_bins, double p, 
 // fill the lanes of one "wave row" (s steps), classes sorted by their extension
 // counts so the lanes' extension loops match, and the wave rows go to the 16 waves
 // of the workgroup longest first onto the least-loaded wave.  Slot s of a pass is
-// step s / 1024 of thread s % 1024 (count.hip kSlabThreads); idle slots keep both
+// step s / kSlabThreads of thread s % kSlabThreads (fa_limits.h); idle slots keep both
 // partial ANDs and have no extensions.  Record flags: kRecKeepQ = the shared
 // m-1 rows are the previous piece's, kRecKeepP = the whole prefix is.
 // ---------------------------------------------------------------------------
 struct SlabPiece { int64_t g, lo, hi; };
-constexpr int kSlabWg = 1024;              // count.hip kSlabThreads
 constexpr int kClsMaxRun = 8;              // pieces per class run (longer classes are cut)
 constexpr double kClsMinGain = 0.8;        // class layout only when its wave-step reads are < 0.8x
 constexpr uint8_t kRecKeepQ = 1, kRecKeepP = 2;
@@ -85,7 +85,7 @@ constexpr uint8_t kRecKeepQ = 1, kRecKeepP = 2;
 // at every slab's barrier.
 static int64_t slot_cost(const std::vector<SlabPiece>& pcs, const std::vector<int64_t>& slots,
                          const std::vector<uint8_t>& flags, int m) {
-  int64_t wc[kSlabWg / 64] = {0};
+  int64_t wc[kSlabThreads / 64] = {0};
   const int64_t n = (int64_t)slots.size();
   for (int64_t w0 = 0; w0 < n; w0 += 64) {
     bool q = false, p = false, any = false;
@@ -97,9 +97,9 @@ static int64_t slot_cost(const std::vector<SlabPiece>& pcs, const std::vector<in
       p = p || !(flags[s] & kRecKeepP);
       e = std::max(e, pcs[slots[s]].hi - pcs[slots[s]].lo);
     }
-    if (any) wc[(w0 % kSlabWg) / 64] += (q ? m - 1 : 0) + (p ? 1 : 0) + e + 1;
+    if (any) wc[(w0 % kSlabThreads) / 64] += (q ? m - 1 : 0) + (p ? 1 : 0) + e + 1;
   }
-  return *std::max_element(wc, wc + kSlabWg / 64);
+  return *std::max_element(wc, wc + kSlabThreads / 64);
 }
 
 static void cls_layout(const std::vector<SlabPiece>& pcs, int64_t i, int64_t j, const int32_t* Pf,
@@ -123,7 +123,7 @@ static void cls_layout(const std::vector<SlabPiece>& pcs, int64_t i, int64_t j, 
   // wave rows of <= 64 runs of one length, costliest first, each to the wave with the
   // least estimated reads so far: the waves meet at every slab's barrier, so the
   // critical path is the busiest wave (slot_cost)
-  constexpr int NWv = kSlabWg / 64;
+  constexpr int NWv = kSlabThreads / 64;
   struct Row { int64_t r0, r1, cost; };
   std::vector<Row> rows;
   for (int64_t r = 0; r < (int64_t)runs.size();) {
@@ -153,8 +153,8 @@ static void cls_layout(const std::vector<SlabPiece>& pcs, int64_t i, int64_t j, 
     wcost[w] += rw.cost;
   }
   const int64_t T = *std::max_element(load, load + NWv);
-  slots.assign((size_t)(T * kSlabWg), -1);
-  flags.assign((size_t)(T * kSlabWg), kRecKeepQ | kRecKeepP);
+  slots.assign((size_t)(T * kSlabThreads), -1);
+  flags.assign((size_t)(T * kSlabThreads), kRecKeepQ | kRecKeepP);
   for (int w = 0; w < NWv; ++w) {
     int64_t t = 0;
     for (const auto& row : rows_of[w]) {
@@ -163,7 +163,7 @@ static void cls_layout(const std::vector<SlabPiece>& pcs, int64_t i, int64_t j, 
         const int64_t lane = r - row.first;
         for (int e = 0; e < s; ++e) {
           const int64_t k = runs[r].k0 + e;
-          const size_t at = (size_t)((t + e) * kSlabWg + w * 64 + lane);
+          const size_t at = (size_t)((t + e) * kSlabThreads + w * 64 + lane);
           slots[at] = k;
           flags[at] = e == 0 ? 0 : (uint8_t)(kRecKeepQ | (pcs[k].g == pcs[k - 1].g ? kRecKeepP : 0));
         }
@@ -231,7 +231,7 @@ FA_API int fa_level_plan(const int32_t* Pf, const int64_t* poff, int64_t G, cons
   }
   const int64_t NP = (int64_t)pcs.size();
   // passes: consecutive pieces while their extensions fit the accumulator; then the
-  // slot order of each pass (slot s = step s / 1024 of thread s % 1024): size-sorted
+  // slot order of each pass (slot s = step s / kSlabThreads of thread s % kSlabThreads): size-sorted
   // pieces, or (class layout, see cls_layout) sibling runs with sharing flags
   // records carry the last prefix item's slab row in 13 bits (bits 19-31 of r[1])
   const bool cls_ok = cls_mode > 0 && uniform && m0 >= 2 && m0 <= 12 && n_used < 8192;

@@ -51,7 +51,6 @@ GRAM_WORDPAIRS_PER_S = 1.7e13
 F1_SKETCH_MIN_VOCAB = 1 << 20
 # numeric vocabularies up to this wide read the whole F1 histogram back at once
 F1_HIST_READBACK = 1 << 16
-F1_MAX_CANDIDATES = ops.primitives.F1_MAX_CANDIDATES
 _TRIU_CACHE: dict = {}
 _POW10 = 10 ** np.arange(1, 11, dtype=np.int64)           # numeric token order (_frequent_items)
 _POW10_PAD = 10 ** (10 - np.arange(0, 12).clip(max=10)).astype(np.int64)
@@ -591,7 +590,7 @@ class FastApriori:
         (capped at TUNING.window_trim_rows_frac; T40I10D100M: ~0.8 for a level-5 window of
         ~370 items, ~0.97 for a level-9 one of ~150).
         (FastApriori.scala:132-160 counts every row per candidate.)"""
-        if bm is None or used_w.size > ops.primitives.WINDOW_MAX_ITEMS:
+        if bm is None or used_w.size > ops.primitives.limits().kWinMaxItems:
             return None
         keep = min(TUNING.window_trim_rows_frac,
                    1.0 - TUNING.window_trim_cost * used_w.size / max(1, n_cand * (k + 1)))
@@ -712,8 +711,8 @@ class FastApriori:
         P.accb = self._dl_accb
         c1 = np.ascontiguousarray(db["c1"], dtype=np.int64)
         alive = np.ascontiguousarray(db["alive"], dtype=np.uint8)
-        hist = db.get("len_hist")
-        hist = np.ascontiguousarray(hist, dtype=np.int64) if hist is not None and hist.size == 256 else None
+        hist, bins = db.get("len_hist"), ops.primitives.limits().kTrimHist
+        hist = np.ascontiguousarray(hist, dtype=np.int64) if hist is not None and hist.size == bins else None
         S.post_keep = (c1, alive, hist)                # alive while the native call reads them
         P.c1, P.alive = c1.ctypes.data, alive.ctypes.data
         P.len_hist = hist.ctypes.data if hist is not None else None
@@ -958,7 +957,7 @@ class FastApriori:
                     if shard.extras.size:
                         hist += torch.bincount(torch.from_numpy(shard.extras.astype(np.int64)), minlength=V).to(dev)
                 comm.all_reduce_(hist)
-                if (dev.type == "cuda" and TUNING.f1_rank_device and 2 <= V <= ops.primitives.F1_RANK_DEVICE_MAX
+                if (dev.type == "cuda" and TUNING.f1_rank_device and 2 <= V <= ops.primitives.limits().kF1RankMax
                         and self.cfg.tiebreak in ("string", "numeric")):
                     # narrow vocabulary: ranked on the device (prep.hip k_f1_rank); the LUT is
                     # there at once and the ranking comes back while compression runs (_run)
@@ -1103,7 +1102,7 @@ class FastApriori:
         thr is a candidate; exact counts of the candidates then decide.  The
         sketch (2 x 16K int64) and the candidate counts are the only all-reduces
         (instead of V int64).  Returns None (-> plain histogram) when the sketch
-        is too crowded to leave at most ops.F1_MAX_CANDIDATES candidates; the
+        is too crowded to leave at most kF1ExactMaxCand candidates (fa_limits.h); the
         decision is identical on every rank since the reduced sketch is."""
         comm, dev = self.dcomm, shard.items.device
         sk = ops.f1_sketch(shard.items)
@@ -1112,7 +1111,7 @@ class FastApriori:
             sk += ops.f1_sketch(ex).to(dev)
         comm.all_reduce_(sk)
         cand = torch.nonzero(ops.sketch_estimate(sk, torch.arange(V, device=dev)) >= thr).flatten()
-        if cand.numel() > F1_MAX_CANDIDATES:
+        if cand.numel() > ops.primitives.limits().kF1ExactMaxCand:
             return None
         cnt = ops.f1_exact(shard.items, cand)
         if ex is not None:
@@ -1155,22 +1154,23 @@ class FastApriori:
             if T:
                 torch.cumsum(cnt[kept.to(torch.int64)].to(torch.int64), 0, out=roff[1:])
             ranks = ops.compress(shard.offsets, shard.items, lut, kept, roff, F1)
-            hist = ops.histogram(torch.clamp(cnt, max=255), 256).cpu().numpy() if cnt.numel() else np.zeros(256, np.int64)
+            bins, n = ops.primitives.limits().kCmpHist, cnt.numel()
+            hist = ops.histogram(torch.clamp(cnt, max=bins - 1), bins).cpu().numpy() if n else np.zeros(bins, np.int64)
             bcnt = None
         db = {"roff": roff, "ranks": ranks, "T": T, "src": None, "ncols": T, "wword": None, "wrow": None,
               "bm": None, "W": 0, "F1": F1, "alive": np.ones(F1, dtype=bool), "c1": self._counts1,
               "bcnt": bcnt}      # 256-item block counts of these rows (pair layout); dropped on re-layout
-        # row-length histogram (lengths >= 255 share the last bin): drives the pair
+        # row-length histogram (kCmpHist bins, the longest rows share the last): drives the pair
         # cost model, the trimming model and the u8 per-block count guard
         hist[:2] = 0                         # rows with < 2 frequent items are not kept
-        L = np.arange(256, dtype=np.int64)
+        L = np.arange(hist.size, dtype=np.int64)
         db["pair_work"] = int((hist * (L * (L - 1) // 2)).sum())
         db["len_hist"] = hist
         # every rank must take the same layout decisions: long rows, dedup and (when the
         # layout stays undeduplicated) the pair strategy, agreed in one collective
         # (the kept rows ride along: without dedup they are also the layout's columns,
         # the run's T / distinct metrics, and _finish needs no collective of its own)
-        g = self.dcomm.all_gather_ints([int(hist[255] > 0), int(self._want_dedup(db)),
+        g = self.dcomm.all_gather_ints([int(hist[-1] > 0), int(self._want_dedup(db)),
                                         int(self._pick_gram_local(db, F1)), db["pair_work"], T])
         db["long_rows"] = bool(g[:, 0].max())
         db["pair_work_all"] = int(g[:, 3].sum())      # pair increments of every rank (bounds |F_2|)
@@ -1197,7 +1197,7 @@ class FastApriori:
             # estimate the distinct fraction on a prefix sample of the rows: linear
             # counting (occupied slots of a 4M-slot bitmap of the row hashes: one
             # scatter + one sum, instead of sorting the sample)
-            m = 1 << 22
+            m = ops.primitives.limits().kProbeBits
             probe = getattr(self, "_dedup_probe", None)
             if probe and probe.get("n"):
                 n, filled = probe["n"], probe["filled"]      # computed with the compression (device)

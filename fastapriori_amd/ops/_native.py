@@ -50,6 +50,8 @@ _HOST_SIGS = {
     "fa_trim_estimate": (None, [vp, i64, dbl, C.c_int, C.POINTER(dbl), C.POINTER(dbl)]),
     # the device bundle loop's slots, limits, mode bits and struct layouts by name (csrc/host/fa_dl.h)
     "fa_dl_layout": (cp, [C.c_int, I64P]),
+    # the kernels' capacity limits and pads by name (csrc/host/fa_limits.h)
+    "fa_limits": (cp, [C.c_int, I64P]),
     "fa_f1_rank_numeric": (i64, [vp, i64, i64, vp, vp, vp]),
     "fa_rules_build": (vp, [vp, vp, vp, C.c_int, vp, C.c_int, vp]),
     "fa_rules_nante": (i64, [vp]),
@@ -133,7 +135,6 @@ _HIP_SIGS = {
     "fa_hip_recommend_topn_indexed": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, vp, vp, i64, i32, vp, vp]),
     "fa_hip_parse_tiles": (i64, [i64]),
     "fa_hip_tparse_tiles": (i64, [i64, i64]),
-    "fa_hip_tparse_hist_cap": (C.c_int, []),
     "fa_hip_tline_count": (C.c_int, [vp, i64, i64, vp, vp]),
     "fa_hip_tparse": (C.c_int, [vp, i64, i64, i64, C.c_int, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "fa_hip_scan_small": (C.c_int, [C.c_int, vp, i64, vp, vp, vp]),

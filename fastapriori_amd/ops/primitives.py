@@ -110,9 +110,6 @@ def histogram(items: torch.Tensor, V: int) -> torch.Tensor:
     return out
 
 
-F1_RANK_DEVICE_MAX = 2048   # prep.hip kF1RankMax
-
-
 class F1Pending:
     """The device F1 ranking of f1_rank_start: the id -> rank LUT is on the device
     already (kernels that read it can be queued); finish() waits for the ranking's copy
@@ -136,7 +133,7 @@ def f1_rank_start(hist: torch.Tensor, thr: int, numeric_tiebreak: bool) -> F1Pen
     FastApriori.scala:55-62's order, csrc/host/f1.cpp fa_f1_rank_numeric's) and queue
     the ranking's copy to pinned memory, without waiting (F1Pending)."""
     V = hist.numel()
-    assert hist.is_cuda and hist.dtype == _I64 and 1 <= V <= F1_RANK_DEVICE_MAX and thr >= 1
+    assert hist.is_cuda and hist.dtype == _I64 and 1 <= V <= limits().kF1RankMax and thr >= 1
     dev = hist.device
     lut = torch.empty(V, dtype=_I32, device=dev)
     pack = torch.empty(2 * V + 1, dtype=_I64, device=dev)
@@ -153,37 +150,33 @@ def f1_rank_start(hist: torch.Tensor, thr: int, numeric_tiebreak: bool) -> F1Pen
 # ---------------------------------------------------------------------------
 # Heavy-hitter F1 (wide vocabularies; csrc/hip/prep.hip k_f1_sketch/k_f1_exact)
 # ---------------------------------------------------------------------------
-SK_LOG = 14                      # sketch bins per row (2 rows)
-SK_A = (0x9E3779B1, 0x85EBCA77)  # multiplicative hash constants (mirrored in prep.hip)
-F1_MAX_CANDIDATES = 1 << 13      # exact-pass LDS table: 16K slots at load <= 0.5
-
-
-def sk_hash(ids: torch.Tensor, a: int, log: int = SK_LOG) -> torch.Tensor:
-    """(uint32(id) * a) >> (32 - log), as int64."""
-    return ((ids.to(_I64) * a) & 0xFFFFFFFF) >> (32 - log)
+def sk_hash(ids: torch.Tensor, a: int) -> torch.Tensor:
+    """(uint32(id) * a) >> (32 - kSkLog), as int64: a row's bin (a: kSkA0 / kSkA1)."""
+    return ((ids.to(_I64) * a) & 0xFFFFFFFF) >> (32 - limits().kSkLog)
 
 
 def f1_sketch(items: torch.Tensor) -> torch.Tensor:
-    """2-row count-min sketch of the ids in ``items`` -> int64 [2, 2**SK_LOG]."""
-    W = 1 << SK_LOG
+    """2-row count-min sketch of the ids in ``items`` -> int64 [2, 2**kSkLog]."""
+    L = limits()
+    W = 1 << L.kSkLog
     if items.is_cuda:
         nwg = C.c_int(0)
-        partial = torch.empty(256 * 2 * W, dtype=_I32, device=items.device)
+        partial = torch.empty(L.kSkGridMax * 2 * W, dtype=_I32, device=items.device)
         _hip_call("fa_hip_f1_sketch", _p(items), items.numel(), _p(partial), C.addressof(nwg), _stream(items))
         # per-workgroup counts < 2^31 (a workgroup sees at most nnz/nwg tokens)
         return partial[: nwg.value * 2 * W].view(max(nwg.value, 1), 2, W).sum(0, dtype=_I64) if nwg.value else \
             torch.zeros(2, W, dtype=_I64, device=items.device)
-    return torch.stack([torch.bincount(sk_hash(items, a), minlength=W) for a in SK_A])
+    return torch.stack([torch.bincount(sk_hash(items, a), minlength=W) for a in (L.kSkA0, L.kSkA1)])
 
 
 def sketch_estimate(sk: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
-    return torch.minimum(sk[0][sk_hash(ids, SK_A[0])], sk[1][sk_hash(ids, SK_A[1])])
+    return torch.minimum(sk[0][sk_hash(ids, limits().kSkA0)], sk[1][sk_hash(ids, limits().kSkA1)])
 
 
 def f1_exact(items: torch.Tensor, cand: torch.Tensor) -> torch.Tensor:
     """Exact occurrence counts of the (distinct) ids ``cand`` in ``items`` -> int64 [len(cand)]."""
     n = cand.numel()
-    assert n <= F1_MAX_CANDIDATES
+    assert n <= limits().kF1ExactMaxCand
     if n == 0:
         return torch.zeros(0, dtype=_I64, device=items.device)
     if items.is_cuda:
@@ -191,7 +184,7 @@ def f1_exact(items: torch.Tensor, cand: torch.Tensor) -> torch.Tensor:
         ids = cand.to(_I64).cpu().contiguous()
         keys = torch.empty(1 << log_s, dtype=_I32)
         slot = torch.empty(n, dtype=_I64)
-        _native.host().fa_build_probe_table(_p(ids), n, log_s, SK_A[0], _p(keys), _p(slot))
+        _native.host().fa_build_probe_table(_p(ids), n, log_s, limits().kSkA0, _p(keys), _p(slot))
         counts = torch.zeros(1 << log_s, dtype=_I32, device=items.device)
         _hip_call("fa_hip_f1_exact", _p(items), items.numel(), _p(keys.to(items.device)), log_s, _p(counts),
                   _stream(items))
@@ -218,7 +211,6 @@ def txn_freq_count(offsets: torch.Tensor, items: torch.Tensor, lut: torch.Tensor
     return out
 
 
-COMPRESS_WAVE_MAX_F1 = 65536
 # mean row length above which the 64-token staged tier (64 KB input span per workgroup) runs first
 COMPRESS_STAGED64_MEAN_LEN = 16.0
 
@@ -228,8 +220,8 @@ def compress(offsets, items, lut, kept, roff, F1: int | None = None) -> torch.Te
 
     Device tiers (csrc/hip/prep.hip), chosen by row length L: L <= 16 LDS-staged
     register sort; L <= 64 register bitonic network; longer rows one wave per
-    row with an LDS rank bitmap (no sort; F1 <= 65536) or, for wider F1, a
-    workgroup LDS bitonic sort.  Long-document data (mean L large) skips the
+    row with an LDS rank bitmap (no sort; F1 <= kCwMaxF1) or, for wider F1, a
+    workgroup LDS bitonic sort (rows up to kLongMax tokens).  Long-document data (mean L large) skips the
     first two tiers."""
     T = kept.numel()
     nnz = int(roff[-1].item()) if T else 0
@@ -241,7 +233,7 @@ def compress(offsets, items, lut, kept, roff, F1: int | None = None) -> torch.Te
                                        num_threads())
         return ranks[:nnz]
     st = _stream(items)
-    wave_ok = F1 is not None and F1 <= COMPRESS_WAVE_MAX_F1
+    wave_ok = F1 is not None and F1 <= limits().kCwMaxF1
     if wave_ok and items.numel() > TUNING.compress_wave_mean_len * max(offsets.numel() - 1, 1):
         _hip_call("fa_hip_compress_wave", _p(offsets), _p(items), _p(lut), None, T, _p(kept), _p(roff),
                   _p(ranks), F1, None, st)
@@ -274,14 +266,9 @@ def compress(offsets, items, lut, kept, roff, F1: int | None = None) -> torch.Te
             _hip_call("fa_hip_compress_lds", _p(offsets), _p(items), _p(lut), _p(over2), n2, _p(kept),
                       _p(roff), _p(ranks), _p(over3), _p(n_over3), st)
             n3 = int(n_over3.item())
-            if n3:   # rows longer than 16384 tokens: sorted by torch, row by row
+            if n3:   # rows longer than kLongMax tokens: sorted by torch, row by row
                 _compress_torch(offsets, items, lut, kept, roff, ranks, over3[:n3])
     return ranks[:nnz]
-
-
-PAIR_PAD_BATCHES = 3 * 16 + 2   # the pair kernel's pipeline reads up to this many batches past a chunk
-# the emit pass of compress_rows also writes the pair kernel's blocked layout (TUNING.fused_layout off: the
-# separate block-scatter pass of pair_counts_horizontal)
 
 
 @dataclass
@@ -289,7 +276,8 @@ class BlockLayout:
     """The k = 2 blocked layout of compressed rows (pair_counts_horizontal): cnt = u8
     [nb * T + pad] per-row counts of 256-rank blocks; lr / base (optional) = the local
     ranks (u8, block-major, row order) and the int64 [nb * ceil(T / 64) + pad] 64-row
-    batch bases, written by compress_rows' emit pass (no block-scatter pass)."""
+    batch bases, written by compress_rows' emit pass (TUNING.fused_layout; off: the
+    block-scatter pass of pair_counts_horizontal).  Pads: fa_limits.h kPairPadBatches."""
     cnt: torch.Tensor
     lr: torch.Tensor | None = None
     base: torch.Tensor | None = None
@@ -299,26 +287,26 @@ class BlockLayout:
 
 
 # rows hashed by the dedup estimate (FastApriori._want_dedup): linear counting of 2^18
-# row hashes in 2^22 slots estimates the distinct fraction to ~0.03 % (one standard
-# error); the probe is a fixed cost per rank (1M rows: 0.22 ms)
+# row hashes in kProbeBits slots estimates the distinct fraction to ~0.03 % (one standard
+# error); the probe is a fixed cost per rank (1M rows: 0.22 ms); at most kProbeMaxRows
 DEDUP_PROBE_ROWS = 1 << 18
 
 
 def compress_rows(offsets, items, lut, F1: int, block_counts: bool = True, probe: dict | None = None):
     """compress_rows_finish(compress_rows_start(...)).  Fused two-pass compression (device, short rows; csrc/hip/prep.hip k_cmp_agg /
     k_cmp_emit): returns (kept int32 [T], roff int64 [T+1], ranks int32 [nnz],
-    length histogram (host int64 [256]), bcnt) with one host synchronisation.  Rows
+    length histogram (host int64 [kCmpHist]), bcnt) with one host synchronisation.  Rows
     of more than 16 tokens are finished by the register / wave tiers of ``compress``
     (the rows the register tier leaves go to the wave tier by flag, no compaction).
 
-    bcnt (block_counts and F1 <= 2048, else None): uint8 [nb * T + pad], the
+    bcnt (block_counts and at most kCmpMaxNB blocks, else None): uint8 [nb * T + pad], the
     per-row item counts of 256-rank blocks that the pair kernel's blocked layout
     needs (pair_counts_horizontal), written by the emit pass while the sorted row
     is in registers instead of by a separate pass over the ranks.
 
     probe (a dict): also run the dedup probe (prep.hip k_dedup_probe) over the first
     min(T, DEDUP_PROBE_ROWS) rows, read back with the sizes: probe["n"] rows hashed,
-    probe["filled"] occupied slots of its 2^22-slot bitmap."""
+    probe["filled"] occupied slots of its kProbeBits-slot bitmap."""
     return compress_rows_finish(compress_rows_start(offsets, items, lut, F1, block_counts, probe))
 
 
@@ -330,18 +318,20 @@ def compress_rows_start(offsets, items, lut, F1: int, block_counts: bool = True,
     nwg = (n + 255) // 256
     st = _stream(items)
     nb = (F1 + 255) // 256
-    blk = block_counts and 1 <= nb <= 8 and n > 0
+    L = limits()
+    pad = L.kPairPadBatches * 64 + L.kPairCntSpare
+    blk = block_counts and 1 <= nb <= L.kCmpMaxNB and n > 0
     fused = blk and TUNING.fused_layout
     agg = torch.empty(3 * max(nwg, 1), dtype=_I32, device=dev)
     aggb = torch.empty(nb * nwg, dtype=_I32, device=dev) if fused else None
-    hist = torch.zeros(64, 256, dtype=_I32, device=dev)
+    hist = torch.zeros(L.kCmpStripes, L.kCmpHist, dtype=_I32, device=dev)
     _hip_call("fa_hip_cmp_agg", _p(offsets), _p(items), _p(lut), n, _p(agg), _p(hist), _p(aggb), nb, st)
     # exclusive scans of the aggregates (and block totals) + roff[0] = 0: prep.hip fa_hip_cmp_scan
     pre = torch.empty(3, nwg + 1, dtype=_I64, device=dev)
     preb = torch.empty(nb * nwg + 1, dtype=_I64, device=dev) if fused else None
     kept = torch.empty(max(n, 1), dtype=_I32, device=dev)
     roff = torch.empty(n + 1, dtype=_I64, device=dev)
-    part = torch.empty(4 * ((max(nb, 1) * max(nwg, 1) + 4095) // 4096 + 1), dtype=_I64, device=dev)
+    part = torch.empty(4 * (-(-max(nb, 1) * max(nwg, 1) // L.kScanChunk) + 1), dtype=_I64, device=dev)
     _hip_call("fa_hip_cmp_scan", _p(agg), _p(aggb), max(nwg, 1) if n > 0 else 0, nb, _p(part), _p(pre), _p(preb),
               _p(roff), st)
     if n <= 0:
@@ -352,11 +342,11 @@ def compress_rows_start(offsets, items, lut, F1: int, block_counts: bool = True,
     bcnt = lr = lbase = ovb = None
     lr_cap = 0
     if blk:
-        bcnt = torch.empty(nb * max(n, 1) + PAIR_PAD_BATCHES * 64 + 64, dtype=torch.uint8, device=dev)
+        bcnt = torch.empty(nb * max(n, 1) + pad, dtype=torch.uint8, device=dev)
     if fused:
         lr_cap = max(items.numel(), 1)
-        lr = torch.empty(lr_cap + 1024, dtype=torch.uint8, device=dev)   # pad: aligned dword staging reads
-        lbase = torch.zeros(nb * ((n + 63) // 64) + PAIR_PAD_BATCHES, dtype=_I64, device=dev)
+        lr = torch.empty(lr_cap + L.kPairLrPad, dtype=torch.uint8, device=dev)   # pad: aligned dword staging reads
+        lbase = torch.zeros(nb * ((n + 63) // 64) + L.kPairPadBatches, dtype=_I64, device=dev)
         ovb = torch.empty(max(n, 1) * nb, dtype=_I64, device=dev)
     _hip_call("fa_hip_cmp_emit", _p(offsets), _p(items), _p(lut), n, _p(pre[0]), _p(pre[1]), _p(pre[2]), _p(kept),
               _p(roff), _p(ranks), _p(over), _p(bcnt), nb, _p(preb), _p(lr), lr_cap, _p(lbase), _p(ovb), st)
@@ -364,6 +354,7 @@ def compress_rows_start(offsets, items, lut, F1: int, block_counts: bool = True,
         # the kernel reads T = pre[0, -1] on the device and hashes the rows the emit
         # pass has finished (<= 16 items; the later tiers write the longer ones)
         # scratch: the rows' slots + per-workgroup row counts (prep.hip, no zeroing)
+        assert DEDUP_PROBE_ROWS <= L.kProbeMaxRows
         ws = torch.empty(DEDUP_PROBE_ROWS + (DEDUP_PROBE_ROWS + 255) // 256, dtype=_I32, device=dev)
         tail = torch.zeros(2, dtype=_I64, device=dev)
         _hip_call("fa_hip_dedup_probe", _p(roff), _p(ranks), pre[0].data_ptr() + 8 * (pre.shape[1] - 1),
@@ -378,7 +369,7 @@ def compress_rows_start(offsets, items, lut, F1: int, block_counts: bool = True,
     ev.record()
     host.event = ev
     return dict(offsets=offsets, items=items, lut=lut, F1=F1, probe=probe, got=got, ev=ev, kept=kept, roff=roff,
-                ranks=ranks, over=over, bcnt=bcnt, lr=lr, lbase=lbase, ovb=ovb, lr_cap=lr_cap, nb=nb, st=st)
+                ranks=ranks, over=over, bcnt=bcnt, lr=lr, lbase=lbase, ovb=ovb, lr_cap=lr_cap, nb=nb, st=st, pad=pad)
 
 
 def compress_rows_finish(c: dict):
@@ -398,7 +389,7 @@ def compress_rows_finish(c: dict):
                                                                    "lr_cap"))
     kept, roff, ranks = kept[:T], roff[:T + 1], ranks[:nnz]
     if bcnt is not None:
-        bcnt = bcnt[:nb * T + PAIR_PAD_BATCHES * 64 + 64]
+        bcnt = bcnt[:nb * T + c["pad"]]
         bcnt[nb * T:].zero_()
         layout = BlockLayout(bcnt, lr, lbase)
     out = kept, roff, ranks, hist_h, (layout if bcnt is not None else None)
@@ -423,7 +414,7 @@ def _compress_rows_overflow(offsets, items, lut, F1, kept, roff, ranks, over, bc
         else:
             _hip_call("fa_hip_compress_regs", 64, _p(offsets), _p(items), _p(lut), _p(over), no, _p(kept), _p(roff),
                       _p(ranks), _p(flag2), st)
-        if F1 <= COMPRESS_WAVE_MAX_F1:
+        if F1 <= limits().kCwMaxF1:
             # rows of > 64 tokens (flag2) through the wave tier and the block counts, by
             # flag: no compaction, no host synchronisation
             _hip_call("fa_hip_compress_wave", _p(offsets), _p(items), _p(lut), _p(over), no, _p(kept), _p(roff),
@@ -557,9 +548,9 @@ def pair_counts_horizontal(roff, ranks, wrow, F1: int, long_rows: bool = True, b
             nb = (F1 + pb - 1) // pb
             nbatch = (T + 63) // 64
             # cnt / base are padded past their ends: the pair kernel's software
-            # pipeline loads up to 3 x 16 batches past a chunk unconditionally (those
-            # values are never processed; padded bases must be valid lr offsets)
-            pad_b = PAIR_PAD_BATCHES
+            # pipeline loads batches past a chunk unconditionally (those values are
+            # never processed; padded bases must be valid lr offsets)
+            pad_b, lr_pad = limits().kPairPadBatches, limits().kPairLrPad
             lay = bcnt if isinstance(bcnt, BlockLayout) else None
             if lay is not None:
                 bcnt = lay.cnt
@@ -581,7 +572,7 @@ def pair_counts_horizontal(roff, ranks, wrow, F1: int, long_rows: bool = True, b
                 base[:nb * nbatch] -= bsum
                 # every rank lands in exactly one block: the layout holds all of them (no readback)
                 total = int(ranks.numel())
-                lr = torch.empty(total + 1024, dtype=torch.uint8, device=dev)   # pad: aligned dword staging reads
+                lr = torch.empty(total + lr_pad, dtype=torch.uint8, device=dev)   # pad: aligned dword staging reads
                 _hip_call("fa_hip_block_scatter", _p(roff), _p(ranks), T, F1, _p(cnt), _p(base), _p(lr), pb, st)
             if pb == 256:
                 # work-queue schedule: persistent workgroups keep their tile across
@@ -712,7 +703,7 @@ def pair_counts_gram(bm: torch.Tensor, W: int, wword, wcls=None, force_popc: boo
     return out
 
 
-def _split_groups(ext_off: np.ndarray, per_block: int, max_block_ext: int = 1024):
+def _split_groups(ext_off: np.ndarray, per_block: int, max_block_ext: int):
     """Host-side work split for the candidate kernel.
 
     Groups with more than ``max_block_ext`` extensions are cut into several
@@ -753,8 +744,8 @@ def count_candidates(bm: torch.Tensor, W: int, prefix: torch.Tensor, ext_off: np
         return torch.zeros(0, dtype=_I64, device=dev)
     if bm.is_cuda:
         nsc = max(1, (W + 2047) // 2048)
-        per_block = int(np.clip(C * nsc // 4096, 16, 1024))
-        gidx, new_off, starts = _split_groups(ext_off, per_block)
+        per_block = int(np.clip(C * nsc // 4096, 16, limits().kMaxBlockExt))
+        gidx, new_off, starts = _split_groups(ext_off, per_block, limits().kMaxBlockExt)
         pre = prefix[torch.from_numpy(gidx).to(dev)].contiguous() if gidx.size != prefix.shape[0] else prefix
         off_t = torch.from_numpy(new_off).to(dev)
         st_t = torch.from_numpy(starts).to(dev)
@@ -769,23 +760,21 @@ def count_candidates(bm: torch.Tensor, W: int, prefix: torch.Tensor, ext_off: np
     return out
 
 
-TRIM_HIST_BINS = 256   # csrc/hip/prep.hip kTrimHist
-
-
 def trim_rows(roff, ranks, alive: torch.Tensor, min_len: int, wrow=None):
     """Keep rows with >= min_len alive items, dropping the dead items.
 
     alive: int8 [F1] on the rows' device.  Returns (kept row ids int32, new roff,
-    new ranks, new wrow, histogram of new row lengths int64 [256], lengths >= 255
+    new ranks, new wrow, histogram of new row lengths int64 [kTrimHist], longer ones
     in the last bin) — ranks stay sorted within each row.  Device path: count ->
     scan of 256-row block sums -> emit (csrc/hip/prep.hip k_trim_scan_count /
     k_trim_emit), one host sync for the output sizes.
     """
     T = roff.numel() - 1
     dev = ranks.device
+    bins = limits().kTrimHist
     if T == 0:
         return (torch.zeros(0, dtype=_I32, device=dev), roff, ranks, wrow,
-                torch.zeros(TRIM_HIST_BINS, dtype=_I64, device=dev))
+                torch.zeros(bins, dtype=_I64, device=dev))
     if ranks.is_cuda:
         st = _stream(ranks)
         nb = (T + 255) // 256
@@ -802,7 +791,7 @@ def trim_rows(roff, ranks, alive: torch.Tensor, min_len: int, wrow=None):
         nroff[K:] = nnz
         nranks = torch.empty(max(nnz, 1), dtype=_I32, device=dev)
         kept = torch.empty(max(K, 1), dtype=_I32, device=dev)
-        hist = torch.zeros(64, TRIM_HIST_BINS, dtype=_I64, device=dev)
+        hist = torch.zeros(limits().kTrimStripes, bins, dtype=_I64, device=dev)
         if K:
             _hip_call("fa_hip_trim_emit", _p(roff), _p(ranks), _p(alive), F1, T, _p(cnt), _p(bases[0]), _p(bases[1]),
                       _p(nroff), _p(nranks), _p(kept), _p(hist), st)
@@ -830,8 +819,8 @@ def trim_rows(roff, ranks, alive: torch.Tensor, min_len: int, wrow=None):
         em = torch.repeat_interleave(rowmask, lens) & (alive[ranks.to(_I64)] > 0)
         nranks[:nnz] = ranks[em]
     nw = wrow[kept.to(_I64)].contiguous() if wrow is not None else None
-    hist = torch.bincount(cnt[kept.to(_I64)].to(_I64).clamp_(max=TRIM_HIST_BINS - 1),
-                          minlength=TRIM_HIST_BINS) if K else torch.zeros(TRIM_HIST_BINS, dtype=_I64)
+    hist = torch.bincount(cnt[kept.to(_I64)].to(_I64).clamp_(max=bins - 1),
+                          minlength=bins) if K else torch.zeros(bins, dtype=_I64)
     return kept, nroff, nranks[:nnz], nw, hist
 
 
@@ -1092,8 +1081,8 @@ def count_level(roff, ranks, src, ncols: int, F1: int, prefix: np.ndarray, ext_o
 
 
 def ag_mark_words(F1: int) -> int:
-    """u32 words of the chain's used-item bitset (gen.hip ag_mark_words)."""
-    return max(128, (F1 + 31) // 32)
+    """u32 words of the chain's used-item bitset (fa_limits.h ag_mark_words)."""
+    return max(limits().kAgMarkMinWords, (F1 + 31) // 32)
 
 # Device -> host fallbacks taken by the current phase (a mining run or a rules
 # phase clears the list when it starts, reset_fallbacks(), and reports what it
@@ -1414,16 +1403,6 @@ def _compact_lines(scratch, xscratch, bound_off, dcnt, xcnt, nl, st):
     return off, items, extras
 
 
-PARSE_HIST_CAP = None       # kHistCap of the tile parser's fused F1 histogram (parse.hip)
-
-
-def parse_hist_cap() -> int:
-    global PARSE_HIST_CAP
-    if PARSE_HIST_CAP is None:
-        PARSE_HIST_CAP = int(_native.hip().fa_hip_tparse_hist_cap())
-    return PARSE_HIST_CAP
-
-
 class TileParse:
     """The tile parser's per-region steps (csrc/hip/parse.hip k_tline_count,
     k_tparse, k_tcompact), all queued on one stream.  Line counts come either
@@ -1431,7 +1410,7 @@ class TileParse:
     of the region's '\n' bytes (streamed regions: no readback at all).  Items of
     every region are written at a device-side running offset into one buffer
     sized by the upper bound (bytes + 1) / 2; the F1 histogram (items and repeats,
-    ids < parse_hist_cap()) accumulates per compaction block."""
+    ids < kHistCap) accumulates per compaction block."""
 
     GRID = 1024       # compaction workgroups (rows of the histogram partials): 4 per CU
 
@@ -1439,7 +1418,7 @@ class TileParse:
         self.buf, self.n, self.dev = buf, n, dev
         self.st = _stream(buf)
         self.lib = _native.hip()
-        cap = parse_hist_cap()
+        cap = limits().kHistCap
         tok_cap = (n + 1) // 2 + 1           # tokens are separated: at most (bytes + 1) / 2
         self.items = torch.empty(tok_cap, dtype=_I32, device=dev)
         # repeated ids are rare: a small buffer, and a second parse in the rare file that overflows it
@@ -1515,7 +1494,7 @@ class TileParse:
         V = mx + 1 if self.n_lines else 0       # no lines: an empty vocabulary (as the host parser)
         hist = None
         if not over:
-            cap = parse_hist_cap()
+            cap = limits().kHistCap
             hist = torch.empty(cap, dtype=_I64, device=dev)
             _native.check(self.lib.fa_hip_hist_reduce(_p(self.hpart), self.GRID, _p(hist), self.st),
                           "fa_hip_hist_reduce")
@@ -1593,21 +1572,34 @@ def parse_dict_device(buf: torch.Tensor, n: int, last_is_term: bool):
 # csrc/hip/levels.hip fa_hip_dl_plan / fa_hip_dl_threshold; driven by
 # models.apriori.FastApriori._mine_device)
 # ---------------------------------------------------------------------------
-class _DlLayout:
-    """csrc/host/fa_dl.h by name, read from libfa_host.so (fa_dl_layout) at first use: the
-    control block's slots (kDlStop ..), the limits and the slab count's mode bits as
-    attributes under their C++ names; desc_dtype, the level table's record type (DlDesc);
-    post_size / post_offsets, DlPost's layout; table, every exported (name, value)."""
+class _NativeTable:
+    """A by-name table of libfa_host.so, read at first use: table, every exported (name,
+    value); the constants as attributes under their C++ names."""
 
-    def __init__(self):
-        lib, v, i = _native.host(), ctypes.c_int64(0), 0
+    def __init__(self, export):
+        v, i = ctypes.c_int64(0), 0
         self.table = {}
-        while (name := lib.fa_dl_layout(i, ctypes.byref(v))) is not None:
+        while (name := export(i, ctypes.byref(v))) is not None:
             self.table[name.decode()] = int(v.value)
             i += 1
         for name, val in self.table.items():
             if name.isidentifier():
                 setattr(self, name, val)
+
+
+@functools.lru_cache(maxsize=None)
+def limits() -> _NativeTable:
+    """csrc/host/fa_limits.h (fa_limits): the kernels' capacity limits and pads."""
+    return _NativeTable(_native.host().fa_limits)
+
+
+class _DlLayout(_NativeTable):
+    """csrc/host/fa_dl.h (fa_dl_layout): the control block's slots (kDlStop ..), the limits
+    and the slab count's mode bits; desc_dtype, the level table's record type (DlDesc);
+    post_size / post_offsets, DlPost's layout."""
+
+    def __init__(self):
+        super().__init__(_native.host().fa_dl_layout)
         desc = sorted((off, n[7:]) for n, off in self.table.items() if n.startswith("DlDesc."))
         self.desc_dtype = np.dtype(dict(names=[n for _, n in desc], formats=[np.int64] * len(desc),
                                         offsets=[off for off, _ in desc], itemsize=self.table["sizeof(DlDesc)"]))
@@ -1642,7 +1634,7 @@ class DlPostC(ctypes.Structure):
 
 class DeviceLevelState:
     """Per-device buffers of the device bundle loop, reused across mining runs:
-    the generator workspace, the control block (+ its pinned host mirror), the
+    the generator workspace, the control block (+ its pinned host copy), the
     per-level F sizes (fsz[k] = |F_k| on the device) and the post-step's plan and
     count buffers (DlPostC; sized for one accumulator pass)."""
 
@@ -1863,7 +1855,6 @@ def dl_count_multipass(S: DeviceLevelState, F1: int, n_used: int, C: int, lds: i
 
 
 WINDOW_SAMPLE = 16   # window_bitmap: the share of the words (1 / this) that decides max_keep
-WINDOW_MAX_ITEMS = 2047   # count.hip k_win_alive: bit-sliced counts of up to 11 planes
 
 
 def window_bitmap(bm: torch.Tensor, rows_w: torch.Tensor, W: int, k: int, max_keep: int | None = None,

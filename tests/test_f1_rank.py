@@ -68,6 +68,7 @@ def test_device_rank_matches_host(V, hi, thr, numeric):
     same ids and supports in rank order, the same id -> rank LUT (many ties at hi = 3)."""
     import torch
     from fastapriori_amd.ops import primitives as P
+    assert (V == P.limits().kF1RankMax) == (V == 2048)
     hh = np.random.default_rng(V + hi).integers(0, hi, V).astype(np.int64)
     hh[min(V - 1, 10)] = hi + 5                       # a sure frequent id
     pend = P.f1_rank_start(torch.from_numpy(hh).cuda(), thr, numeric)

@@ -161,8 +161,10 @@ def test_parser_histogram_counts_occurrences(tmp_path):
 
 
 def test_wide_ids_skip_the_parser_histogram(tmp_path):
-    p = _write(tmp_path, b"1 2 3\n9000 2\n")      # id 9001 >= the LDS histogram's 8192 bins
+    p = _write(tmp_path, b"1 2 3\n9000 2\n")      # id 9001 >= the LDS histogram's kHistCap bins
     g = _same(p)
+    from fastapriori_amd.ops import primitives as prim
+    assert 9001 >= prim.limits().kHistCap > 3
     assert g.hist is None
 
 

@@ -603,8 +603,8 @@ def test_scan_small_int64_carry(K, with_base):
 
 # ---------------------------------------------------------------------------
 # 8. level 0 of the device loop, nothing past it (max_levels = 1): k_dl_decide0 up to
-#    4 * kDsBlk = 16384 parent rows (by n_bound), k_ds_blocks / k_ds_decide0 / k_ds_add
-#    in 4096-row blocks past it.  The reference is the host generator on the same rows.
+#    4 * kDsBlk parent rows (by n_bound; fa_limits.h), k_ds_blocks / k_ds_decide0 / k_ds_add
+#    in kDsBlk-row blocks past it.  The reference is the host generator on the same rows.
 # ---------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def _level0_case(n):
@@ -636,6 +636,7 @@ LEVEL0_CASES = [(n, n, False) for n in (3, 1023, 1024, 1025, 2049)] + \
 @pytest.mark.parametrize("n,n_bound,from_device", LEVEL0_CASES)
 def test_dl_level0(dl_state, n, n_bound, from_device):
     rows, F1, cnt, cand = _level0_case(n)
+    assert (n_bound > 4 * prim.limits().kDsBlk) == (n_bound == 16385) and (n > prim.limits().kDsBlk) == (n > 4096)
     if n > 1000:
         assert (cnt == 0).mean() > 0.1 and set(range(5)) <= set(cnt.tolist())
     S, K, C = dl_state, prim.dl(), len(cand)

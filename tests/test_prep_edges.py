@@ -11,7 +11,9 @@ input is built on purpose from per-row token lists (seeded where random): an inp
 iff row t holds a token with lut == r, in numpy, never from another path of this project.
 All values are integers and every comparison is exact equality over the whole output.
 Every builder asserts that it reaches the edge it is named for; a builder that steers a
-dispatch asserts the gate's inequality with the constant restated next to it.
+dispatch asserts the gate's inequality; a gate that is a kernel limit is read by name from
+prim.limits() (csrc/host/fa_limits.h) inside the builder, and the literal shapes keep the
+case on the limit.
 
 Ops with a CPU path run on "cpu" too: that proves the builders and the references where
 there is no GPU.  The device-only families (compress_rows, item_map / blocked bitmaps) have
@@ -257,12 +259,11 @@ def test_txn_freq_count(native, name, dev):
 # 2. compress: the tier chain by mean row length
 # ---------------------------------------------------------------------------
 CMP_STAGED64_MEAN = 16.0     # primitives.py COMPRESS_STAGED64_MEAN_LEN: nnz > 16 * n -> the 64-token staged tier
-CMP_WAVE_MEAN = 48.0         # tuning.py compress_wave_mean_len: nnz > 48 * n (and F1 <= 65536) -> every row by k_compress_wave
-CMP_WAVE_MAX_F1 = 65536      # primitives.py COMPRESS_WAVE_MAX_F1
+CMP_WAVE_MEAN = 48.0         # tuning.py compress_wave_mean_len: nnz > 48 * n (and F1 <= kCwMaxF1) -> every row by k_compress_wave
 
 
 def _cmp_tier(case, F1arg):
-    if F1arg is not None and F1arg <= CMP_WAVE_MAX_F1 and case.nnz > CMP_WAVE_MEAN * case.n:
+    if F1arg is not None and F1arg <= prim.limits().kCwMaxF1 and case.nnz > CMP_WAVE_MEAN * case.n:
         return "wave"
     return "staged64" if case.nnz > CMP_STAGED64_MEAN * case.n else "staged16"
 
@@ -382,6 +383,7 @@ def _cmp_wave(f1):
     assert set(case.L[ref.kept].tolist()) == {49, 256, 257, 600} and (ref.c == 1).sum() == 4
     assert ref.Bk[:, edge].all(1).sum() >= 4 and ref.Bk[:, f1 - 1].sum() >= 8     # a row per length holds every edge rank
     assert (f1 + 4095) // 4096 == {64: 1, 4096: 1, 4097: 2, 65536: 16}[f1]
+    assert (f1 == prim.limits().kCwMaxF1) == (f1 == 65536)
     return case, f1, "wave"
 
 
@@ -399,22 +401,23 @@ def _cmp_wave_many():
 
 
 def _cmp_wide():
-    # F1 = 66000 > 65536: no wave tier.  Rows of 65, 16384 and 16385 tokens go by flag to
-    # k_compress_lds, which sorts up to 16384 tokens and leaves the last row to torch
+    # F1 = 66000 > kCwMaxF1: no wave tier.  Rows of 65, 16384 and 16385 tokens go by flag to
+    # k_compress_lds, which sorts up to kLongMax tokens and leaves the last row to torch
     rng = np.random.default_rng(2700)
     f1 = 66000
     lut, freq, infreq = _make_lut(rng, 70000, f1)
     rows = [_row(rng, freq, infreq, 65, 60, ranks=(0, f1 - 1)), _row(rng, freq, infreq, 16384, 15000, ranks=(0, f1 - 1)),
             _row(rng, freq, infreq, 16385, 16385, ranks=(0, f1 - 1)), _row(rng, freq, infreq, 100, 1)]
     case = _from_rows(rows, lut, f1)
-    assert f1 > CMP_WAVE_MAX_F1 and _cmp_tier(case, f1) == "staged64"
+    assert sorted(case.L.tolist())[-2:] == [prim.limits().kLongMax, prim.limits().kLongMax + 1]
+    assert f1 > prim.limits().kCwMaxF1 and _cmp_tier(case, f1) == "staged64"
     return case, f1, "staged64"
 
 
 CMP_CASES = {
     "staged16_T1": lambda: _cmp_short(1), "staged16_T255": lambda: _cmp_short(255),
     "staged16_T256": lambda: _cmp_short(256), "staged16_T257": lambda: _cmp_short(257),
-    # kCSpan = 8192 tokens (prep.hip): staged at 8191 and 8192, read row by row at 8193
+    # kCSpan tokens: staged at 8191 and 8192, read row by row at 8193
     "staged16_spans": lambda: _cmp_span(16, 16, (8191, 8192, 8193), 300, "staged16"),
     "staged16_long_rows_wave": lambda: _cmp_long_flags(300),
     "staged16_long_rows_lds": lambda: _cmp_long_flags(None),
@@ -449,9 +452,7 @@ def test_compress_tiers(native, name, dev):
 # ---------------------------------------------------------------------------
 # 3. compress_rows: k_cmp_agg / the three-kernel scan / k_cmp_emit and the fused layout
 # ---------------------------------------------------------------------------
-CMP_SPAN = 4096          # prep.hip kCmpSpan: a workgroup's 256 rows are staged up to 4096 tokens
-CMP_MID_PER_WAVE = 8     # prep.hip kCmpMidPerWave
-SCAN_CHUNK = 4096        # prep.hip kScanChunk
+# kCmpSpan: a workgroup's 256 rows are staged up to that many tokens; kCmpMidPerWave; kScanChunk
 PROBE_ROWS = 1 << 18     # primitives.py DEDUP_PROBE_ROWS
 
 
@@ -520,7 +521,7 @@ def _fused_lengths():
         rows += [_row(rng, freq, infreq, *specs[i]) for i in order]
         rows += _short_rows(rng, freq, infreq, 256 - len(specs), 0, 4)
     case = _from_rows(rows, lut, 300)
-    assert case.n == 512 and max(_wg_tokens(case)) <= CMP_SPAN
+    assert case.n == 512 and max(_wg_tokens(case)) <= prim.limits().kCmpSpan
     ref = _reference(case)
     for r0 in (0, 256):
         L, c = case.L[r0:r0 + 256], ref.c[r0:r0 + 256]
@@ -551,7 +552,7 @@ def _fused_mid_counts():
     rows += [_row(rng, freq, infreq, 17 + k % 4, 2 + k % 3) for k in range(64)]
     case = _from_rows(rows, lut, 300)
     assert _mid_per_wave(case, _reference(case)).tolist() == [7, 8, 9, 64]
-    assert _wg_tokens(case)[0] <= CMP_SPAN
+    assert _wg_tokens(case)[0] <= prim.limits().kCmpSpan
     return case
 
 
@@ -573,8 +574,8 @@ def _fused_mid_slots():
     ref = _reference(case)
     k32 = ((ref.c >= 2) & (case.L >= 17) & (case.L <= 32)).reshape(-1, 64).sum(1)
     k64 = ((ref.c >= 2) & (case.L >= 33) & (case.L <= 64)).reshape(-1, 64).sum(1)
-    assert list(zip(k32.tolist(), k64.tolist())) == want and max(_wg_tokens(case)) <= CMP_SPAN
-    assert (k32 + k64).max() <= CMP_MID_PER_WAVE
+    assert list(zip(k32.tolist(), k64.tolist())) == want and max(_wg_tokens(case)) <= prim.limits().kCmpSpan
+    assert (k32 + k64).max() <= prim.limits().kCmpMidPerWave
     return case
 
 
@@ -611,7 +612,7 @@ def _fused_full_output():
     rows = [_row(rng, freq, infreq, 16, 16) for _ in range(256)] + _short_rows(rng, freq, infreq, 40)
     case = _from_rows(rows, lut, 300)
     ref = _reference(case)
-    assert _wg_tokens(case)[0] == CMP_SPAN and int(ref.c[:256].sum()) == CMP_SPAN
+    assert _wg_tokens(case)[0] == prim.limits().kCmpSpan and int(ref.c[:256].sum()) == prim.limits().kCmpSpan
     return case
 
 
@@ -697,7 +698,7 @@ def _fused_block_scan_chunks():
     lut = rng.permutation(V).astype(np.int32)
     case = _case(off, items, lut, V)
     nwg = (n + 255) // 256
-    assert not case.dense and 8 * nwg > SCAN_CHUNK >= nwg
+    assert not case.dense and 8 * nwg > prim.limits().kScanChunk >= nwg
     return case
 
 
@@ -710,7 +711,7 @@ def _fused_all_scan_chunks():
     off, items = _rand_rows(rng, lens, 3)
     lut = np.array([1, 2, 0], np.int32)
     case = _case(off, items, lut, 3)
-    assert (n + 255) // 256 > SCAN_CHUNK and case.dense
+    assert (n + 255) // 256 > prim.limits().kScanChunk and case.dense
     return case
 
 
@@ -796,7 +797,7 @@ def _pairs_sparse(roff, ranks, F1):
 
 def _fused_reference(case):
     ref = _reference(case)
-    if case.F1 <= 2048:
+    if case.F1 <= 256 * prim.limits().kCmpMaxNB:
         ref.cnt, ref.lr, ref.base = (_layout_dense(ref.Bk, case.F1) if case.dense
                                      else _layout_sparse(ref.roff, ref.ranks, case.F1))
         ref.pairs = _gram(ref.Bk) if case.dense else _pairs_sparse(ref.roff, ref.ranks, case.F1)
@@ -836,7 +837,7 @@ def _probe_reference(ref):
     sub_off = _excl(np.diff(roff)[sel])
     idx = np.repeat(roff[sel], np.diff(roff)[sel]) + (np.arange(sub_off[-1]) - np.repeat(sub_off[:-1], np.diff(roff)[sel]))
     h1, _ = _np_row_hash(sub_off, ref.ranks[idx])
-    return int(sel.size), int(np.unique(h1 & ((1 << 22) - 1)).size)
+    return int(sel.size), int(np.unique(h1 & (prim.limits().kProbeBits - 1)).size)
 
 
 @pytest.mark.parametrize("name", list(FUSED_CASES))
@@ -855,7 +856,7 @@ def test_fused_reference_invariants(name):
             assert all(np.array_equal(getattr(sp, k), getattr(ref, k)) for k in ("c", "kept", "roff", "ranks", "hist"))
     x = np.repeat(np.arange(T), np.diff(ref.roff))
     assert ((np.diff(ref.ranks) > 0) | (np.diff(x) > 0)).all()          # ranks ascend inside every row
-    if case.F1 > 2048:
+    if case.F1 > 256 * prim.limits().kCmpMaxNB:
         return
     nb, nbatch = ref.cnt.shape[0], (T + 63) // 64
     assert ref.lr.size == nnz and ref.base.size == nb * nbatch and np.array_equal(ref.cnt.sum(0), np.diff(ref.roff))
@@ -889,7 +890,7 @@ def test_compress_rows_fused(name, dev):
     if probe is not None:
         want_n, want_filled = _probe_reference(ref)
         assert (probe["n"], probe["filled"]) == (want_n, want_filled)
-    if F1 > 2048 or case.n == 0:
+    if F1 > 256 * prim.limits().kCmpMaxNB or case.n == 0:
         assert layout is None
         return
     nb, nbatch = (F1 + 255) // 256, (T + 63) // 64
@@ -1080,7 +1081,7 @@ def test_build_bitmaps_item_map(k, with_src, dev):
 # ---------------------------------------------------------------------------
 # 6. trim_rows: k_trim_scan_count / k_trim_emit (64-row waves over 64-rank windows)
 # ---------------------------------------------------------------------------
-TRIM_ALIVE_LDS = 32768     # prep.hip kTrimAliveLds: alive flags in LDS up to F1 = 32768
+# kTrimAliveLds: alive flags in LDS up to F1 = 32768
 
 
 def _rows_dense(rng, lens, F1):
@@ -1150,7 +1151,7 @@ def _trim_wide(F1):
         B[x] = 0
         B[x, rk] = 1
     assert (B[:6] & alive).sum(1).tolist() == [2, 1, 0, 1, 2, 3]
-    assert (F1 <= TRIM_ALIVE_LDS) == (F1 == 32768)
+    assert (F1 <= prim.limits().kTrimAliveLds) == (F1 == 32768)
     return B, alive
 
 
@@ -1190,7 +1191,7 @@ def test_trim_rows(native, name, min_len, weighted, dev):
 # ---------------------------------------------------------------------------
 # 7. histogram: k_histogram (four LDS copies, one LDS copy, global atomics)
 # ---------------------------------------------------------------------------
-HIST_LDS_BINS = 16384      # prep.hip kLdsBins: LDS bins up to V = 16384, four copies while 4 V <= 4096
+# kLdsBins: LDS bins up to V = 16384, four copies while 4 V <= 4096
 
 
 @pytest.mark.parametrize("dev", BOTH)
@@ -1201,7 +1202,8 @@ def test_histogram(native, V, nnz, dev):
     items = rng.integers(0, V, nnz).astype(np.int32)
     if nnz >= 3:
         items[:3] = [0, V - 1, V - 1]
-    assert (V * 4 <= HIST_LDS_BINS // 4) == (V <= 1024) and (V <= HIST_LDS_BINS) == (V <= 16384)
+    bins = prim.limits().kLdsBins
+    assert (V * 4 <= bins // 4) == (V <= 1024) and (V <= bins) == (V <= 16384)
     got = ops.histogram(_t(items, dev), V)
     assert got.dtype == torch.int64 and np.array_equal(got.cpu().numpy(), np.bincount(items, minlength=V))
 
