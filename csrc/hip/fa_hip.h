@@ -234,6 +234,19 @@ __device__ __forceinline__ uint32_t xcd_remap(uint32_t orig, uint32_t nwg) {
   return base + orig / nx;
 }
 
+// Lexicographic compare of the (k-1)-row `a` with row S minus position p: the step of
+// the "subset index" binary search, S - {S[p]} in the sorted level below (rules.hip
+// k_rule_gen reads the found row's count, condense.hip k_sup_mark marks the found row).
+__device__ __forceinline__ int cmp_skip(const int32_t* __restrict__ a, const int32_t* __restrict__ s, int k,
+                                        int p) {
+  for (int i = 0, j = 0; i < k - 1; ++i, ++j) {
+    if (j == p) ++j;
+    const int32_t x = a[i], y = s[j];
+    if (x != y) return x < y ? -1 : 1;
+  }
+  return 0;
+}
+
 struct DlDesc;   // ../host/fa_dl.h
 
 }  // namespace fa

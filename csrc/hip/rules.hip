@@ -23,17 +23,6 @@ namespace fa {
 
 constexpr int kRuleTPB = 256;
 
-// Lexicographic compare of the (k-1)-row `a` with row S minus position p.
-__device__ __forceinline__ int cmp_skip(const int32_t* __restrict__ a, const int32_t* __restrict__ s, int k,
-                                        int p) {
-  for (int i = 0, j = 0; i < k - 1; ++i, ++j) {
-    if (j == p) ++j;
-    const int32_t x = a[i], y = s[j];
-    if (x != y) return x < y ? -1 : 1;
-  }
-  return 0;
-}
-
 // One thread per (itemset s, position p) of level k.  Rows of a wave share
 // the same few itemsets, so the binary-search probes of neighbouring lanes
 // mostly hit the same cache lines of level k-1.

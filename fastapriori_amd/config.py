@@ -84,6 +84,8 @@ class JobConfig:
     tiebreak: str = "string"                    # rank order of equal-count items (utils.jvm.item_tiebreak_key)
     top_n: int = 0                              # > 0: also write <out>recommendsTopN (ranked lists, 1..64 items)
     top_n_scores: bool = False                  # ... every entry as token:confidence
+    closed: bool = False                        # also write <out>closedItemset ("a b[cnt]": no superset of equal count)
+    maximal: bool = False                       # also write <out>maximalItemset ("a b[cnt]": no frequent superset)
     extra: dict = field(default_factory=dict)
 
 
@@ -123,6 +125,14 @@ def build_parser() -> argparse.ArgumentParser:
                         "consequents with distinct items, in rule order, or 0 when none fires")
     p.add_argument("--top-n-scores", action="store_true",
                    help="with --top-n: write every entry as token:confidence")
+    p.add_argument("--closed", action="store_true",
+                   help="also write <output>closedItemset/: the frequent itemsets with no proper superset of the "
+                        "same count, as 'a b c[count]' lines (lossless: an itemset's count is the largest among "
+                        "its closed supersets). With --max-level L: closed among the itemsets of at most L items")
+    p.add_argument("--maximal", action="store_true",
+                   help="also write <output>maximalItemset/: the frequent itemsets with no frequent proper superset, "
+                        "as 'a b c[count]' lines. With --max-level L: maximal among the itemsets of at most L items "
+                        "(every level-L itemset is written)")
     return p
 
 
@@ -139,4 +149,4 @@ def parse_args(argv=None) -> JobConfig:
                      rules_only=a.rules_only, checkpoint=a.checkpoint, overwrite=a.overwrite,
                      profile=a.profile, metrics_path=a.metrics_path, max_level=a.max_level,
                      strategy=a.strategy, world_size=a.world_size, tiebreak=a.tiebreak, top_n=a.top_n,
-                     top_n_scores=a.top_n_scores)
+                     top_n_scores=a.top_n_scores, closed=a.closed, maximal=a.maximal)

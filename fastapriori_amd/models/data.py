@@ -161,6 +161,44 @@ class MiningResult:
             h.update(np.ascontiguousarray(cnt[idx], dtype="<i8").tobytes())
         return h.hexdigest()
 
+    def condensed(self, kind: str, device=None) -> "MiningResult":
+        """The closed or the maximal frequent itemsets of this result (no counterpart in
+        the reference).  ``closed``: no proper superset has the same count -- lossless, an
+        itemset's count is the largest count among its closed supersets.  ``maximal``: no
+        proper superset is frequent.  With a result cut by --max-level both are meant
+        among the itemsets mined: the top level has no mined supersets.
+
+        The marks come from ops.primitives.condense_marks on ``device`` (None: the C++
+        path); the rows are selected there and only the kept ones are copied back.  Every
+        level keeps its place (an emptied one is [0, k]) and its row order."""
+        if kind not in ("closed", "maximal"):
+            raise ValueError(f"condensed: kind must be 'closed' or 'maximal', not {kind!r}")
+        from ..ops import primitives as prim
+        dev = torch.device("cpu" if device is None else device)
+        m = prim.condense_marks(self.levels, self.counts, dev, check=False)
+        base, cbase, K = m["base"], m["cbase"], len(self.levels)
+        ids = torch.nonzero((m["eq"] if kind == "closed" else m["sup"]) == 0).flatten()
+        ids_h = ids.cpu().numpy()
+        cut = np.searchsorted(ids_h, cbase)               # kept ids of level k: [cut[k-1], cut[k])
+        parts = []
+        for k in range(1, K + 1):
+            a, b = int(cut[k - 1]), int(cut[k])
+            if b > a:
+                rows_k = m["rows_all"][int(base[k]):int(base[k + 1])].view(-1, k)
+                parts.append(rows_k[ids[a:b] - int(cbase[k - 1])].reshape(-1))
+        rows_h = torch.cat(parts).cpu().numpy() if parts else np.zeros(0, dtype=np.int32)
+        cnt_h = m["cnt_all"][ids].cpu().numpy()
+        prim.condense_check(m)                            # after the last readback
+        levels, counts, o = [], [], 0
+        for k in range(1, K + 1):
+            a, b = int(cut[k - 1]), int(cut[k])
+            levels.append(rows_h[o:o + (b - a) * k].reshape(-1, k).copy())
+            counts.append(cnt_h[a:b].copy())
+            o += (b - a) * k
+        return MiningResult(items=self.items, levels=levels, counts=counts, min_count=self.min_count,
+                            n_lines=self.n_lines, stats={"condensed": kind, "n_all": self.n_itemsets},
+                            item_hashes=self.item_hashes)
+
     def as_dict(self) -> dict[frozenset, int]:
         out = {}
         for rows, cnt in zip(self.levels, self.counts):

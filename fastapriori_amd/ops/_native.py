@@ -60,6 +60,7 @@ _HOST_SIGS = {
     "fa_rules_free": (None, [vp]),
     "fa_recommend_cpu": (None, [vp, vp, vp, i64, i32, vp, vp, i64, vp, C.c_int]),
     "fa_recommend_topn_cpu": (None, [vp, vp, vp, i64, i32, vp, vp, i64, i32, vp, C.c_int]),
+    "fa_condense_cpu": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, vp, C.c_int]),
     "fa_write_freq_itemsets": (C.c_int, [cp, vp, vp, i32, vp, vp, vp, C.c_int, C.c_int, C.c_int]),
     "fa_cpu_histogram": (None, [vp, i64, i64, vp, C.c_int]),
     "fa_build_probe_table": (None, [vp, i64, C.c_int, C.c_uint32, vp, vp]),
@@ -149,6 +150,7 @@ _HIP_SIGS = {
     "fa_hip_rule_gen": (C.c_int, [vp, i64, C.c_int, vp, i64, vp, vp, vp, vp, vp]),
     "fa_hip_rule_cut": (C.c_int, [vp, vp, i64, C.c_int, vp, vp, vp, vp]),
     "fa_hip_rule_emit": (C.c_int, [vp, vp, vp, vp, vp, i64, vp, vp]),
+    "fa_hip_sup_mark": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]),
 }
 
 

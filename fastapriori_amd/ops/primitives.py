@@ -1361,6 +1361,84 @@ def rules_build_device(levels: list, counts: list, tie_pos: np.ndarray, dev) -> 
                 level_stats=stats, level_ms=level_ms)
 
 
+def condense_marks(levels: list, counts: list, dev, check: bool = True) -> dict:
+    """The superset marks behind the closed and the maximal itemsets (csrc/hip/condense.hip
+    k_sup_mark on a device, csrc/host/condense.cpp fa_condense_cpu on ``cpu``; no counterpart
+    in the reference).
+
+    levels / counts as rules_build_device.  One upload (the rows, and the counts with the
+    level tables), one launch for all levels.  Returns tensors on ``dev`` in that layout:
+    rows_all int32, cnt_all int64, sup / eq uint8 [n_itemsets] (sup[t]: itemset t has a
+    frequent superset, eq[t]: it has one of equal count), the host tables base [K+2]
+    (element offset of the size-m level at [m]) and cbase [K+1] (row offset of the size-m
+    level at [m-1]), and err (the device error word, None on ``cpu``).
+
+    An input that is not downward closed or not sorted raises RuntimeError: here when
+    ``check``, else in condense_check, which the caller runs after its last readback
+    (it reads the error word, which waits for the kernel)."""
+    dev = torch.device(dev)
+    K = len(levels)
+    sizes = np.array([len(c) for c in counts], dtype=np.int64).reshape(-1)
+    lv = [np.ascontiguousarray(l, dtype=np.int32).reshape(-1) for l in levels]
+    if len(sizes) != K or any(l.size != int(sizes[k]) * (k + 1) for k, l in enumerate(lv)):
+        raise ValueError("condense_marks: levels[k-1] must be [n_k, k] with n_k counts")
+    base = np.zeros(K + 2, dtype=np.int64)            # base[m]: element offset of the size-m level
+    np.cumsum([l.size for l in lv], out=base[2:K + 2])
+    cbase = np.zeros(K + 1, dtype=np.int64)
+    np.cumsum(sizes, out=cbase[1:])
+    eoff = np.zeros(K + 2, dtype=np.int64)            # eoff[k]: first (itemset, position) index of level k >= 2
+    for k in range(2, K + 1):
+        eoff[k + 1] = eoff[k] + int(sizes[k - 1]) * k
+    n = int(cbase[K])
+    rows_h = np.concatenate(lv) if lv else np.zeros(0, dtype=np.int32)
+    tab_h = np.concatenate([np.asarray(c, dtype=np.int64).reshape(-1) for c in counts] + [base, cbase, eoff])
+    rows_all = torch.from_numpy(rows_h).to(dev)
+    tab = torch.from_numpy(tab_h).to(dev)
+    flags = torch.zeros(2 * n, dtype=torch.uint8, device=dev)
+    out = dict(rows_all=rows_all, cnt_all=tab[:n], sup=flags[:n], eq=flags[n:], base=base, cbase=cbase, err=None,
+               tab=tab, sizes=sizes)
+    if dev.type == "cuda":
+        out["err"] = torch.zeros(1, dtype=_I32, device=dev)
+    _condense_launch(out)
+    if check:
+        condense_check(out)
+    return out
+
+
+def _condense_launch(m: dict) -> None:
+    """The marks of condense_marks' uploaded state ``m``: tab holds the counts, then base
+    [K+2], cbase [K+1] and the first (itemset, position) index of every level [K+2]."""
+    K, n, p0 = len(m["sizes"]), m["cnt_all"].numel(), m["tab"].data_ptr()
+    p_base, p_cbase, p_eoff = p0 + 8 * n, p0 + 8 * (n + K + 2), p0 + 8 * (n + 2 * K + 3)
+    if m["err"] is not None:
+        rc = _native.hip().fa_hip_sup_mark(_p(m["rows_all"]), p_base, p0, p_cbase, p_eoff, m["sizes"].ctypes.data, K,
+                                           _p(m["sup"]), _p(m["eq"]), _p(m["err"]), _stream(m["rows_all"]))
+        if rc == 3:
+            raise RuntimeError("fa_hip_sup_mark: a level has 2^31 - 1 rows or more (the subset index is int32)")
+        _native.check(rc, "fa_hip_sup_mark")
+    else:
+        m["bad_level"] = int(_native.host().fa_condense_cpu(_p(m["rows_all"]), p_base, p0, p_cbase, K, _p(m["sup"]),
+                                                            _p(m["eq"]), num_threads()))
+
+
+def condense_check(marks: dict) -> None:
+    """Raise when condense_marks met an itemset with a subset missing from the level below."""
+    bad = int(marks["err"].item()) if marks["err"] is not None else marks.get("bad_level", 0)
+    if bad:
+        raise RuntimeError(f"condense: an itemset of size {bad} has a subset that is not in level {bad - 1} "
+                           "(the levels are not downward closed, or a level is not sorted)")
+
+
+def condense_flags(levels: list, counts: list, dev) -> list:
+    """Per level k the pair (has_superset, has_equal_superset): uint8 tensors [n_k] on ``dev``.
+    An itemset is maximal iff has_superset is 0 and closed iff has_equal_superset is 0; the top
+    level, a single-level result and trailing empty levels are all zeros.  A device runs
+    k_sup_mark (one launch for all levels), ``cpu`` the C++ path; see condense_marks."""
+    m = condense_marks(levels, counts, dev)
+    cb = m["cbase"]
+    return [(m["sup"][int(cb[k]):int(cb[k + 1])], m["eq"][int(cb[k]):int(cb[k + 1])]) for k in range(len(levels))]
+
+
 def _device_lines(buf: torch.Tensor, n: int, last_is_term: bool):
     """Line ends of n file bytes in HBM and per-line upper-bound slots of (len + 1) / 2
     ids: (ends int64 [nl], nl, bound_off int64 [nl + 1], total slots)."""

@@ -132,6 +132,35 @@ def recommend_window(cfg: JobConfig, comm, log: Logger, result, summary: dict) -
     return recs
 
 
+CONDENSED_DIRS = {"closed": "closedItemset", "maximal": "maximalItemset"}
+
+
+def condense_window(cfg: JobConfig, comm, log: Logger, result, summary: dict) -> None:
+    """--closed / --maximal (no counterpart in the reference): between its two timed
+    windows, so neither gets slower.  Every rank holds the identical result: rank 0
+    alone computes on its device and writes ``<output>closedItemset`` /
+    ``<output>maximalItemset`` ("a b c[cnt]" lines, the format io.load_saved_results
+    reads back); the others meet it where it reports how that went."""
+    for kind in [k for k in ("closed", "maximal") if getattr(cfg, k)]:
+        t0 = time.perf_counter()
+        n_kept, err = None, None
+        if comm.is_root:
+            try:
+                kept = result.condensed(kind, device=comm.device)
+                io.write_freq_itemsets(kept, cfg.output + CONDENSED_DIRS[kind], with_counts=True,
+                                       overwrite=cfg.overwrite)
+                n_kept = kept.n_itemsets
+            except (OSError, RuntimeError, ValueError) as e:
+                err = f"{type(e).__name__}: {e}"
+        n_kept, err = comm.broadcast_object((n_kept, err))     # the ranks' meeting point
+        if err:
+            raise RuntimeError(f"--{kind} failed on rank 0: {err}")
+        ms = int((time.perf_counter() - t0) * 1000)
+        log.line(f"Total time for get {kind}Itemsets {ms}")
+        log.metric(phase="condense", kind=kind, n_all=result.n_itemsets, n_kept=n_kept, ms=ms)
+        summary[f"n_{kind}"] = n_kept
+
+
 def make_checkpointer(cfg: JobConfig, comm) -> Checkpointer | None:
     if cfg.temp and (cfg.checkpoint or cfg.rules_only):
         # rules-only needs no D.dat: it reloads the mined itemsets (Utils.getAll's use case)
@@ -172,6 +201,9 @@ def run_job(cfg: JobConfig, comm=None) -> dict:
             result = mine_window(cfg, comm, log, ckpt, summary)
         t_mine = int((time.time() - t1) * 1000)
         log.line(f"Total time for get freqItemsets {t_mine}")
+
+        if cfg.closed or cfg.maximal:
+            condense_window(cfg, comm, log, result, summary)
 
         t2 = time.time()
         recommend_window(cfg, comm, log, result, summary)
