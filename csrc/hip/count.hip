@@ -1419,6 +1419,17 @@ __device__ __forceinline__ void slab_copy_bm(uint4* lds4, int n_used, const uint
 // load after its last piece fetches its first piece for the next slab.  The
 // rank -> slab-row map of the slab build is copied to LDS as u16 (one dependent
 // global load less per rank).
+//
+// Accumulators (kAccB bytes each, in LDS): 4 = one u32 per candidate, 2 = two u16 per
+// word, 1 = one byte per candidate.  The byte form rests on a single-writer invariant:
+// a thread owns the same pieces on every slab (g = g0 + i * gstep depends on the
+// thread only), and every candidate index lies in exactly one piece's range
+// [a.x, a.x + n_ext) -- levels.hip k_dl_pieces_emit writes cand + 8 * j with the
+// piece's share of the prefix's extensions, and plan.cpp's records cut a group's
+// extensions the same way.  So inside a workgroup a counter has one writer for the
+// whole kernel and is updated by a plain byte read, add and write: no LDS atomic, no
+// periodic drain.  A sum that would pass 255 goes to out[e] whole, with one global
+// atomic, and the byte restarts at 0; the final flush adds what is left.
 // ---------------------------------------------------------------------------
 constexpr int kMapLdsMax = kSlabMapMaxF1;   // fa_slab.h: F1 <= this keeps the map in LDS
 
@@ -1439,7 +1450,7 @@ __device__ __forceinline__ int u16_at(const int4& v, int k) {
   return (k & 1) ? (int)((uint32_t)w >> 16) : (w & 0xFFFF);
 }
 
-template <int SW, bool kWeighted, int kBuild, bool kCls = false, bool kAcc16 = false>
+template <int SW, bool kWeighted, int kBuild, bool kCls = false, int kAccB = 4>
 __global__ __launch_bounds__(kSlabThreads) void k_count_slab_rec(
     const int64_t* __restrict__ roff, const int32_t* __restrict__ ranks, const int32_t* __restrict__ src,
     int64_t ncols, const int32_t* __restrict__ item_map, int F1, int n_used, const int32_t* __restrict__ gpre,
@@ -1453,14 +1464,18 @@ __global__ __launch_bounds__(kSlabThreads) void k_count_slab_rec(
   constexpr int SWP = SW + 2;                       // row stride: odd number of 16-B slots
   constexpr int RS = SWP / 2;
   uint64_t* slab = reinterpret_cast<uint64_t*>(lds4);
-  // kAcc16 (flags & kSlabFlagAcc16): two u16 counters per accumulator word (unit weights; twice the
+  // kAccB = 2 (flags & kSlabFlagAcc16): two u16 counters per accumulator word (unit weights; twice the
   // candidates per accumulator pass), drained into the u32 global counts before they can
   // carry: a slab adds at most SW * 64 to a counter.  A template parameter: a runtime
   // flag put a scalar branch pair around every accumulator add of the extension loop.
-  constexpr bool acc16 = !kWeighted && kAcc16;
-  const int nacc = acc16 ? (C + 1) >> 1 : C;
+  // kAccB = 1: four single-writer byte counters per word (unit weights; see above).
+  static_assert(kAccB == 4 || kAccB == 2 || kAccB == 1, "accumulator bytes");
+  constexpr bool acc16 = !kWeighted && kAccB == 2;
+  constexpr bool acc8 = !kWeighted && kAccB == 1;
+  const int nacc = acc16 ? (C + 1) >> 1 : acc8 ? (C + 3) >> 2 : C;
   constexpr int kFlush16 = 65535 / (SW * 64);
   uint32_t* acc = reinterpret_cast<uint32_t*>(slab + (size_t)n_used * SWP);
+  uint8_t* acc8p = reinterpret_cast<uint8_t*>(acc);
   uint16_t* smap = reinterpret_cast<uint16_t*>(acc + ((nacc + 3) & ~3));
   const bool map_lds = kBuild == kBuildContig && F1 <= kMapLdsMax;
   for (int i = threadIdx.x; i < nacc; i += blockDim.x) acc[i] = 0;
@@ -1516,14 +1531,29 @@ __global__ __launch_bounds__(kSlabThreads) void k_count_slab_rec(
     }
   };
   auto acc_add = [&](int e, uint32_t v) {
-    if (acc16) atomicAdd(&acc[e >> 1], v << ((e & 1) << 4));
-    else atomicAdd(&acc[e], v);
+    if (acc8) {
+      // this thread is counter e's only writer: v <= SW * 64 may itself pass a byte
+      uint32_t t = (uint32_t)acc8p[e] + v;
+      if (t > 255u) { atomicAdd(&out[e], t); t = 0; }
+      acc8p[e] = (uint8_t)t;
+    } else if (acc16) {
+      atomicAdd(&acc[e >> 1], v << ((e & 1) << 4));
+    } else {
+      atomicAdd(&acc[e], v);
+    }
   };
   auto flush = [&]() {
     for (int i = threadIdx.x; i < nacc; i += blockDim.x) {
       const uint32_t v = acc[i];
       if (!v) continue;
-      if (acc16) {
+      if (acc8) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          const uint32_t c = (v >> (8 * b)) & 0xFFu;
+          if (c && 4 * i + b < C) atomicAdd(&out[4 * i + b], c);
+        }
+        acc[i] = 0;
+      } else if (acc16) {
         if (v & 0xFFFFu) atomicAdd(&out[2 * i], v & 0xFFFFu);
         if ((v >> 16) && 2 * i + 1 < C) atomicAdd(&out[2 * i + 1], v >> 16);
         acc[i] = 0;
@@ -2005,7 +2035,8 @@ FA_API int fa_hip_win_compact(const uint64_t* bm, int64_t ld, const int32_t* row
 // and recomputes every prefix, with the same counts).  kSlabDense: dense level, no
 // all-zero-prefix test (the counts are the same either way).  kSlabAcc16: u16 packed
 // accumulators (unit weights: half the LDS per candidate, drained every 65535 / (SW * 64)
-// slabs).
+// slabs).  fa_slab.h kSlabAcc8: single-writer byte accumulators (unit weights: a quarter of
+// the LDS per candidate, no drain).  Weighted rows count into u32 whatever the mode asks.
 // Test hook: at most this many workgroups per slab count (0: no cap).  One workgroup
 // then walks every slab, so the packed-u16 accumulators' mid-run drain (every
 // kFlush16 slabs) runs on inputs of a few hundred thousand rows.
@@ -2031,8 +2062,10 @@ FA_API int fa_hip_count_slab_rec_cls(const int64_t* roff, const int32_t* ranks, 
   // the class-layout flags name a thread's previous piece in the undivided plan: with the
   // pieces divided among ranks the plain kernel recomputes every prefix instead
   if (g_piece_nparts > 1) cls &= ~kSlabCls;
-  const bool acc16 = (cls & kSlabAcc16) && !wword;   // two u16 counters per accumulator word
-  const int64_t n_acc = acc16 ? (C + 1) / 2 : C;
+  // fa_slab.h: u32, two u16 (kSlabAcc16) or four bytes (kSlabAcc8) per accumulator word
+  const int accb = slab_mode_acc_bytes(cls, wword != nullptr);
+  const bool acc16 = accb == 2;
+  const int64_t n_acc = slab_acc_count(C, accb);
   const bool contig = !bm && !src;
   const size_t lds = (size_t)slab_kernel_lds(n_used, sw, slab_acc_words(n_acc), contig ? slab_map_lds(F1) : 0);
   if (lds > 160 * 1024 - 256) return 3;             // static build_words scratch
@@ -2043,10 +2076,12 @@ FA_API int fa_hip_count_slab_rec_cls(const int64_t* roff, const int32_t* ranks, 
   KernT kern = nullptr;
 #define FA_REC_MODE(S, B)                                                                              \
   kern = wword ? (KernT)k_count_slab_rec<S, true, B>                                                   \
-         : (cls & kSlabCls) ? (acc16 ? (KernT)k_count_slab_rec<S, false, B, true, true>                \
-                                     : (KernT)k_count_slab_rec<S, false, B, true, false>)              \
-                            : (acc16 ? (KernT)k_count_slab_rec<S, false, B, false, true>               \
-                                     : (KernT)k_count_slab_rec<S, false, B, false, false>);
+         : (cls & kSlabCls) ? (accb == 1 ? (KernT)k_count_slab_rec<S, false, B, true, 1>               \
+                               : accb == 2 ? (KernT)k_count_slab_rec<S, false, B, true, 2>             \
+                                           : (KernT)k_count_slab_rec<S, false, B, true, 4>)            \
+                            : (accb == 1 ? (KernT)k_count_slab_rec<S, false, B, false, 1>              \
+                               : accb == 2 ? (KernT)k_count_slab_rec<S, false, B, false, 2>            \
+                                           : (KernT)k_count_slab_rec<S, false, B, false, 4>);
 #define FA_REC_CASE(S)                                    \
   if (sw == S) {                                          \
     if (bm) { FA_REC_MODE(S, kBuildBM) }                  \

@@ -1011,7 +1011,7 @@ FA_API int fa_hip_dl_level0(const int32_t* P0, const long long* n_src, int64_t n
 // info[0] = bytes needed) or 7.  post (optional, host DlPost, fa_dl.h): the bundle's
 // plan, trimming decision and count, queued right after the synchronisation.
 static void dl_post(DlPost* P, const DlDesc* desc, int L, long long* ctl, const long long* ch, int F1,
-                    hipStream_t st) {
+                    double accb_rule, hipStream_t st) {
   P->done = 0;
   if (ch[kDlStop] && ch[kDlLevels] == 0) return;   // nothing accepted
   // bound error, multi-pass level, end of mining
@@ -1022,9 +1022,14 @@ static void dl_post(DlPost* P, const DlDesc* desc, int L, long long* ctl, const 
   P->C = C;
   if (C < 1 || C > P->rec_cap || C > P->out_cap || 8 * ((R + 255) / 256) > P->part_cap) return;
   // slab width (fa_slab.h), one accumulator pass
+  // (accb_rule: the bytes per accumulator the bundle was accepted with; P->accb, when
+  // smaller, the accumulators the count may take where they move the slab up to width 16)
   int64_t cap = 0;
-  const int sw = slab_width(n_used, C, P->lds_budget, P->accb, &cap);
+  int sw = slab_width(n_used, C, P->lds_budget, accb_rule, &cap);
   if (sw == 0 || C > cap) return;
+  double accb = accb_rule;
+  if (!P->wword) slab_acc_upgrade(n_used, C, P->lds_budget, P->accb, &sw, &cap, &accb);
+  P->accb = accb;                                  // what the count uses (dl_plan_from_post)
   if (fa_hip_dl_plan(desc, L, ctl, F1, P->item_map, P->rec, C, P->part, P->part_cap, P->gpre, P->gpre_cap, sw,
                      st) != 0)
     return;                                        // (e.g. long prefixes past gpre_cap: the caller plans)
@@ -1054,13 +1059,14 @@ static void dl_post(DlPost* P, const DlDesc* desc, int L, long long* ctl, const 
   }
   if (P->trim) return;                                      // the caller trims, then counts
   const int64_t W = (P->ncols + 63) / 64, nslabs = (W + sw - 1) / sw;
-  const bool acc16 = P->accb == 2.0 && !P->wword;
-  const int64_t nacc = acc16 ? (C + 1) / 2 : C;
+  const bool weighted = P->wword != nullptr;
+  const int64_t nacc = slab_acc_count(C, slab_acc_bytes(P->accb, weighted));
   P->n_wg = slab_workgroups(nslabs, (int64_t)P->lds_kernel,
                             slab_kernel_lds(n_used, sw, slab_acc_words(nacc), slab_map_lds(F1)));
   if (fa_hip_count_slab_rec_cls(P->roff, P->ranks, P->src, P->ncols, P->item_map, F1, (int)n_used, P->gpre, P->rec,
                                 0, (int)C, P->wword, P->out, sw, (int)P->n_wg, nullptr, 0, st, nullptr,
-                                reinterpret_cast<const int32_t*>(ctl + kDlPiecesI32), acc16 ? kSlabAcc16 : 0) != 0)
+                                reinterpret_cast<const int32_t*>(ctl + kDlPiecesI32),
+                                slab_acc_mode(P->accb, weighted)) != 0)
     return;
   P->done = 2;
 }
@@ -1183,6 +1189,6 @@ FA_API int fa_hip_dl_more(int F1, void* ws, int64_t ws_bytes, int64_t ws_used, l
     d.base = desc[l - 1].base + desc[l - 1].C;
   }
   info[0] = w - w0;
-  if (post) dl_post(static_cast<DlPost*>(post), desc, L, ctl, ctl_host, F1, st);
+  if (post) dl_post(static_cast<DlPost*>(post), desc, L, ctl, ctl_host, F1, accb, st);
   FA_LAUNCH_RET();
 }

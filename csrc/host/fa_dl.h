@@ -102,7 +102,10 @@ struct DlPost {
   int64_t done, sw, cap, n_wg, C, trim;
   // prefix slab rows of levels with prefixes past kDlInline ids (levels.hip gpre), int32 [gpre_cap]
   int32_t* gpre; int64_t gpre_cap;
-  // LDS bytes per accumulator: 4, or 2 (unit weights: count.hip's packed u16 counters)
+  // LDS bytes per accumulator: 4, 2 (unit weights: count.hip's packed u16 counters) or 1
+  // (unit weights: single-writer bytes).  In: the narrowest the count may take -- below the
+  // bundling's (fa_hip_dl_more's accb) it is taken where it moves the slab up to width 16
+  // (fa_slab.h slab_acc_upgrade); out: what the plan and the count use
   double accb;
   // trim when the estimate keeps fewer than this share of the rows, or of the items
   // (FastApriori._trim_worth_it, TUNING.trim_rows_frac / trim_nnz_frac)

@@ -40,6 +40,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "fa_dl.h"
+
 #if defined(__HIPCC__)
 #define FA_SLAB_FN __host__ __device__ inline
 #else
@@ -62,7 +64,7 @@ FA_SLAB_FN int64_t slab_map_lds(int64_t F1) {
 }
 
 // Slab width for n_used items and C candidates in lds bytes (accb: LDS bytes per
-// accumulator, 4 or 2): the first width in the measured order whose accumulator
+// accumulator: 4, 2 or 1): the first width in the measured order whose accumulator
 // capacity holds min(C, kSlabBundleTarget), else width 4 from kSlabMinCap4.
 // *cap = that capacity (candidates per pass).  Returns 0 (*cap = 0) when nothing fits.
 FA_SLAB_FN int slab_width(int64_t n_used, int64_t C, double lds, double accb, int64_t* cap) {
@@ -91,6 +93,44 @@ FA_SLAB_FN int64_t slab_total_limit(int64_t n_used, double lds, double accb) {
     if (mid <= slab_cap(n_used, mid, lds, accb)) lo = mid; else hi = mid - 1;
   }
   return lo;
+}
+
+// Accumulator width of a slab count, defined once: accb (the LDS bytes per accumulator
+// the rule above was asked with: 4, 2 or 1) selects the kernel's counters -- u32, two
+// packed u16, or four single-writer bytes per word.  Weighted rows always count into u32.
+// The mode bit rides in fa_hip_count_slab_rec_cls's cls argument: fa_dl.h's kSlabAcc16,
+// or kSlabAcc8 beside it (private: no layer but this header and the launcher names it).
+constexpr int kSlabAcc8 = 8;
+static_assert((kSlabAcc8 & (kSlabCls | kSlabDense | kSlabAcc16)) == 0, "a mode bit of its own");
+
+FA_SLAB_FN int slab_acc_bytes(double accb, bool weighted) {
+  return weighted ? 4 : accb == 1.0 ? 1 : accb == 2.0 ? 2 : 4;
+}
+FA_SLAB_FN int slab_acc_mode(double accb, bool weighted) {
+  const int b = slab_acc_bytes(accb, weighted);
+  return b == 1 ? kSlabAcc8 : b == 2 ? kSlabAcc16 : 0;
+}
+FA_SLAB_FN int slab_mode_acc_bytes(int cls, bool weighted) {
+  return weighted ? 4 : (cls & kSlabAcc8) ? 1 : (cls & kSlabAcc16) ? 2 : 4;
+}
+// u32 words that hold C counters of acc_bytes each (before slab_acc_words' rounding)
+FA_SLAB_FN int64_t slab_acc_count(int64_t C, int acc_bytes) {
+  return acc_bytes == 1 ? (C + 3) / 4 : acc_bytes == 2 ? (C + 1) / 2 : C;
+}
+
+// A one-pass bundle accepted by the rule at *accb bytes per accumulator (slab width *sw,
+// capacity *cap) may count in narrower accumulators of accb_try bytes where that moves its
+// slab up to width 16, the measured best, still in one pass; else it stays as it is.  The
+// bundling itself (which levels share a launch) is the rule's at *accb either way.
+FA_SLAB_FN bool slab_acc_upgrade(int64_t n_used, int64_t C, double lds, double accb_try, int* sw, int64_t* cap,
+                                 double* accb) {
+  if (*sw == 16 || accb_try >= *accb) return false;
+  int64_t c = 0;
+  if (slab_width(n_used, C, lds, accb_try, &c) != 16 || C > c) return false;
+  *sw = 16;
+  *cap = c;
+  *accb = accb_try;
+  return true;
 }
 
 // The kernel's accumulator words for n_acc accumulators (the map after them is 16-B aligned)

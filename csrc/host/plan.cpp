@@ -36,6 +36,17 @@ FA_API int64_t fa_slab_workgroups(int64_t nslabs, int64_t n_used, int sw, int64_
   return slab_workgroups(nslabs, budget,
                          slab_kernel_lds(n_used, sw, round_acc ? slab_acc_words(n_acc) : n_acc, map_bytes));
 }
+// The accumulator width of a slab count asked with accb bytes per accumulator (weighted
+// rows: u32): the cls mode bit of fa_hip_count_slab_rec_cls, and in *n_acc the u32 words
+// that hold C counters
+FA_API int fa_slab_acc_mode(double accb, int weighted, int64_t C, int64_t* n_acc) {
+  if (n_acc) *n_acc = slab_acc_count(C, slab_acc_bytes(accb, weighted != 0));
+  return slab_acc_mode(accb, weighted != 0);
+}
+FA_API int fa_slab_acc_upgrade(int64_t n_used, int64_t C, double lds, double accb_try, int* sw, int64_t* cap,
+                               double* accb) {
+  return slab_acc_upgrade(n_used, C, lds, accb_try, sw, cap, accb) ? 1 : 0;
+}
 FA_API void fa_trim_estimate(const int64_t* len_hist, int64_t n_bins, double p, int k, double* rows, double* nnz) {
   trim_estimate(len_hist, n_bins, p, k, rows, nnz);
 }

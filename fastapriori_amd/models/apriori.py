@@ -396,10 +396,17 @@ class FastApriori:
         lds = Pm.dl_lds_budget(F1)
         # LDS bytes per slab accumulator: packed u16 counters for unit weights (the rows'
         # weighting does not change while mining: trimming keeps the dedup layout) in
-        # window-by-window levels; u32 in one-pass bundles (TUNING.dl_acc16)
+        # window-by-window levels; u32 in one-pass bundles (TUNING.dl_acc16), or
+        # single-writer bytes (TUNING.dl_acc8_bundles) or packed u16 (dl_acc16_bundles)
         unit = db["wword"] is None
         self._dl_mp_accb = 2.0 if TUNING.dl_acc16 and unit else 4.0
-        accb = self._dl_accb = 2.0 if TUNING.dl_acc16_bundles and unit else 4.0
+        acc8 = int(TUNING.dl_acc8_bundles) if unit else 0
+        if int(self._count_view(db)["ncols"]) < TUNING.dl_acc8_min_rows:
+            acc8 = 0
+        accb = self._dl_accb = 1.0 if acc8 == 1 else 2.0 if TUNING.dl_acc16_bundles and unit else 4.0
+        # the narrowest accumulators a bundle's count may take where they move its slab up
+        # to width 16 (fa_slab.h slab_acc_upgrade); the bundling stays the rule's at accb
+        self._dl_cnt_accb = 1.0 if acc8 == 2 else accb
         c_bound = int(lds // accb)
         st = torch.cuda.current_stream(self._dev).cuda_stream
         f2 = self._f2_dev
@@ -465,9 +472,11 @@ class FastApriori:
                 C = int(Cs.sum())
                 done = int(S.post.done) if post else 0
                 sw = int(S.post.sw) if done else 0
+                acc_bytes = int(S.post.accb) if done else int(accb)   # (dl_post writes what it took)
                 if multi is not None:
                     cnt = multi[1]
                     sw = int(Pm.LAST_LEVEL_PLAN.get("sw", 0))
+                    acc_bytes = int(self._dl_mp_accb)
                 elif done == 2:
                     # planned and counted by fa_hip_dl_more's post step (no trim due)
                     cnt = S.post_bufs["out"][:C]
@@ -479,13 +488,13 @@ class FastApriori:
                         plan = Pm.dl_plan_from_post(S, n_used)
                     else:
                         with roctx_range("plan"):
-                            plan = Pm.dl_plan(S, L, F1, n_used, C, lds, self._dev, accb)
+                            plan = Pm.dl_plan(S, L, F1, n_used, C, lds, self._dev, accb, self._dl_cnt_accb)
                     with tm.phase(f"trim{k}"), roctx_range("trim"):
                         self._trim(db, used, k, C, decided=bool(done == 1 and S.post.trim))
                     with tm.phase("count"), roctx_range("count"):
                         v = self._count_view(db)
                         cnt = Pm.dl_count(S, plan, v["roff"], v["ranks"], v["src"], v["ncols"], F1, v["wword"])
-                    sw = int(plan["sw"])
+                    sw, acc_bytes = int(plan["sw"]), int(plan.get("accb", 4.0))
                 # candidate distribution: the candidates this rank counted (non-zero
                 # before the sum; read back with the results, for the stats)
                 nz = torch.count_nonzero(cnt) if self.cand_par else None
@@ -496,7 +505,8 @@ class FastApriori:
             hbm_rows = (db["ranks"].numel() * db["ranks"].element_size()
                         + db["roff"].numel() * db["roff"].element_size())
             pend.append(dict(k=k, L=L, m0=m0, C=Cs, rows=rows_a, cnt=cnt_a, ro=ro, co=co, hbm_rows=int(hbm_rows),
-                             n_par=S.desc["n"][:L].copy(), sw=sw, used=n_used, T=int(db["roff"].numel() - 1),
+                             n_par=S.desc["n"][:L].copy(), sw=sw, acc_bytes=acc_bytes, used=n_used,
+                             T=int(db["roff"].numel() - 1),
                              ms=(time.perf_counter() - t0) * 1e3, bytes=self._bytes_moved() - b0,
                              G=c[K.kDlGl:K.kDlGl + L].copy(), nz=nz))
             P0 = rows_a.data_ptr() + 4 * int(ro[L - 1])
@@ -514,6 +524,9 @@ class FastApriori:
             self.stats["cand_counted"] = int(sum(int(p["nz"]) for p in pend if p["nz"] is not None))
             self.stats["cand_total"] = int(sum(int(p["C"].sum()) for p in pend))
         self.stats["device_bundles"] = len(pend)
+        # (first level, levels, candidates, used items, slab width, accumulator bytes) per bundle
+        self.stats["device_bundle_shapes"] = [(int(p["k"]), int(p["L"]), int(p["C"].sum()), int(p["used"]),
+                                               int(p["sw"]), int(p["acc_bytes"])) for p in pend]
         self.stats["device_levels"] = int(sum(p["L"] for p in pend))
         return nxt
 
@@ -708,7 +721,7 @@ class FastApriori:
         P.src = v["src"].data_ptr() if v["src"] is not None else None
         P.wword = v["wword"].data_ptr() if v["wword"] is not None else None
         P.ncols, P.lds_kernel, P.lds_budget = int(v["ncols"]), float(TUNING.slab_lds_bytes), float(lds)
-        P.accb = self._dl_accb
+        P.accb = self._dl_cnt_accb
         c1 = np.ascontiguousarray(db["c1"], dtype=np.int64)
         alive = np.ascontiguousarray(db["alive"], dtype=np.uint8)
         hist, bins = db.get("len_hist"), ops.primitives.limits().kTrimHist
@@ -855,7 +868,8 @@ class FastApriori:
                 self._level_recs.append((dict(phase="level", k=kk, candidates=int(p["C"][l]), frequent=F,
                                               ms=p["ms"] * share, groups=int(p["G"][l]), bundled_with=p["k"],
                                               bytes_reduced=int(p["bytes"] * share), kernel="slab_rec_dev",
-                                              hbm_bytes_est=hbm, slab_words=p["sw"], used_items=p["used"],
+                                              hbm_bytes_est=hbm, slab_words=p["sw"], acc_bytes=p["acc_bytes"],
+                                              used_items=p["used"],
                                               rows=p["T"], _share=share),
                                          f"level{p['k']}"))
 

@@ -47,6 +47,8 @@ _HOST_SIGS = {
     "fa_slab_total_limit": (i64, [i64, dbl, dbl]),
     "fa_slab_map_lds": (i64, [i64]),
     "fa_slab_workgroups": (i64, [i64, i64, C.c_int, i64, C.c_int, i64, i64]),
+    "fa_slab_acc_mode": (C.c_int, [dbl, C.c_int, i64, I64P]),
+    "fa_slab_acc_upgrade": (C.c_int, [i64, i64, dbl, dbl, C.POINTER(C.c_int), I64P, C.POINTER(dbl)]),
     "fa_trim_estimate": (None, [vp, i64, dbl, C.c_int, C.POINTER(dbl), C.POINTER(dbl)]),
     # the device bundle loop's slots, limits, mode bits and struct layouts by name (csrc/host/fa_dl.h)
     "fa_dl_layout": (cp, [C.c_int, I64P]),

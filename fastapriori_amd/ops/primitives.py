@@ -860,6 +860,15 @@ def _slab_workgroups(nslabs: int, n_used: int, sw: int, n_acc: int, round_acc: b
                                                  int(map_bytes), int(TUNING.slab_lds_bytes)))
 
 
+def _slab_acc_mode(accb: float, weighted: bool, C: int) -> tuple[int, int]:
+    """(fa_hip_count_slab_rec_cls mode bit, u32 accumulator words of C candidates) of a slab
+    count asked with accb LDS bytes per accumulator (fa_slab.h slab_acc_mode: 4 u32, 2 packed
+    u16, 1 single-writer bytes; weighted rows always u32)."""
+    n = ctypes.c_int64(0)
+    mode = _native.host().fa_slab_acc_mode(float(accb), int(bool(weighted)), int(C), ctypes.byref(n))
+    return int(mode), int(n.value)
+
+
 def _slab_dense(wword, sw: int, sup_frac: float) -> bool:
     """count_level's dense test: the slab kernel drops its all-zero-prefix test (sup_frac 0: never)."""
     return wword is None and TUNING.dense_min_rows > 0 and sup_frac * sw * 64 >= TUNING.dense_min_rows
@@ -871,16 +880,16 @@ def _slab_count(*, roff, ranks, src, ncols: int, item_map, F1: int, n_used: int,
     """One slab count (count.hip fa_hip_count_slab_rec_cls) of C candidates over ncols
     columns; roff .. out, g_dev, bm, bm_rows: device addresses or None.  The pieces are
     rec's first G, or as many as the int32 at g_dev says (device plans: ctl's
-    kDlPiecesI32).  accb 2: packed u16 accumulators when the rows have unit weights;
+    kDlPiecesI32).  accb 2: packed u16 accumulators when the rows have unit weights, accb 1:
+    single-writer byte accumulators (fa_slab.h slab_acc_mode; weighted rows count into u32);
     cls: kSlabCls when rec carries class-layout flags; sup_frac: _slab_dense.
     round_acc, map_bytes: what the caller charges a workgroup's LDS (_slab_workgroups;
     csrc/host/fa_slab.h lists the callers' charges)."""
     K = dl()
     nslabs = ((ncols + 63) // 64 + sw - 1) // sw
-    acc16 = accb == 2 and wword is None
-    nacc = (C + 1) // 2 if acc16 else C
+    acc_mode, nacc = _slab_acc_mode(accb, wword is not None, C)
     n_wg = _slab_workgroups(nslabs, n_used, sw, nacc, round_acc, map_bytes)
-    mode = cls | (K.kSlabDense if _slab_dense(wword, sw, sup_frac) else 0) | (K.kSlabAcc16 if acc16 else 0)
+    mode = cls | (K.kSlabDense if _slab_dense(wword, sw, sup_frac) else 0) | acc_mode
     _hip_call("fa_hip_count_slab_rec_cls", roff, ranks, src, ncols, item_map, F1, n_used, gpre, rec, G, C, wword,
               out, sw, n_wg, bm, bm_ld, st, bm_rows, g_dev, mode)
 
@@ -898,13 +907,14 @@ def _level_plan_bound(F1: int, C: int, G: int, m: int) -> int:
 
 
 def level_plan_host(prefix: np.ndarray, ext_off: np.ndarray, ext: np.ndarray, F1: int, W: int,
-                    lds_bytes: int | None = None, poff: np.ndarray | None = None, cls: int | None = None):
+                    lds_bytes: int | None = None, poff: np.ndarray | None = None, cls: int | None = None,
+                    accb: int = 4):
     """fa_level_plan on host arrays (tests / diagnostics): (rc, info, passes, buf)."""
     P, po, G, m = _flat_prefix(prefix, poff)
     C = int(ext.size)
     eo = np.ascontiguousarray(ext_off, dtype=np.int64)
     ex = np.ascontiguousarray(ext, dtype=np.int32)
-    params = _plan_params(lds_bytes or TUNING.slab_lds_bytes, W, TUNING.slab_cls if cls is None else cls)
+    params = _plan_params(lds_bytes or TUNING.slab_lds_bytes, W, TUNING.slab_cls if cls is None else cls, accb)
     bound = _level_plan_bound(F1, C, G, m)
     passes = np.zeros((G + C + 2, 3), np.int64)
     info = np.zeros(24, np.int64)
@@ -919,10 +929,10 @@ def level_plan_host(prefix: np.ndarray, ext_off: np.ndarray, ext: np.ndarray, F1
     return rc, info, passes[:int(info[6])], buf[:int(info[18])]
 
 
-def _plan_params(lds_bytes: int, W: int, cls: int) -> np.ndarray:
+def _plan_params(lds_bytes: int, W: int, cls: int, accb: int = 4) -> np.ndarray:
     """fa_level_plan's params (plan.cpp): LDS bytes, bitmap words, accumulator bytes,
     class layout (0: off, 1: by the wave-step read model, 2: always)."""
-    return np.array([lds_bytes, W, 4.0, cls], dtype=np.float64)
+    return np.array([lds_bytes, W, float(accb), cls], dtype=np.float64)
 
 
 def emulate_level_plan(bits_by_rank: np.ndarray, info, passes, buf, m: int, C: int) -> np.ndarray:
@@ -993,7 +1003,7 @@ def _flat_prefix(prefix: np.ndarray, poff: np.ndarray | None):
 
 def count_level(roff, ranks, src, ncols: int, F1: int, prefix: np.ndarray, ext_off: np.ndarray, ext: np.ndarray,
                 wword, kernel: str = "auto", poff: np.ndarray | None = None, full_bm=None,
-                sup_frac: float = 0.0) -> torch.Tensor | None:
+                sup_frac: float = 0.0, accb: int = 4) -> torch.Tensor | None:
     """Support counts of one level on the device: one native planning call
     (csrc/host/plan.cpp fa_level_plan: used items, slab width, pieces, accumulator
     passes, class layout) into one pinned buffer, one host->device copy, then the
@@ -1009,6 +1019,8 @@ def count_level(roff, ranks, src, ncols: int, F1: int, prefix: np.ndarray, ext_o
     sup_frac: the minimum support as a fraction of the rows; when every frequent prefix
     then expects >= 4 rows per slab (e^-4: ~2 % of a slab's prefixes empty at worst), the
     slab kernel drops its all-zero-prefix test (TUNING.dense_min_rows).
+    accb: LDS bytes per accumulator the level is planned and counted with (4 u32, 2 packed
+    u16, 1 single-writer bytes: fa_slab.h slab_acc_mode); weighted rows count into u32.
     Returns int64 counts [C] (ext order), or None when no LDS slab fits (the
     caller then uses the bitmap kernel)."""
     dev = ranks.device
@@ -1020,7 +1032,10 @@ def count_level(roff, ranks, src, ncols: int, F1: int, prefix: np.ndarray, ext_o
     ex = np.ascontiguousarray(ext, dtype=np.int32)
     W = (ncols + 63) // 64
     # the class layout has no weighted (dedup) kernel: unit weights only
-    params = _plan_params(TUNING.slab_lds_bytes, W, TUNING.slab_cls if wword is None else 0)
+    accb = int(accb) if wword is None else 4
+    if accb not in (1, 2, 4):
+        raise ValueError(f"count_level: accb {accb} (LDS bytes per accumulator: 4, 2 or 1)")
+    params = _plan_params(TUNING.slab_lds_bytes, W, TUNING.slab_cls if wword is None else 0, accb)
     bound = _level_plan_bound(F1, C, G, m)
     on_gpu = dev.type == "cuda"
     stage = pinned_stage("level_plan") if on_gpu else None
@@ -1070,7 +1085,7 @@ def count_level(roff, ranks, src, ncols: int, F1: int, prefix: np.ndarray, ext_o
                     n_used=n_used, gpre=base + 4 * o_gpre, rec=base + 4 * (o_rec + 12 * a), G=b - a,
                     C=bounds[q + 1] - e0, wword=_p(wword), out=out.data_ptr() + 4 * e0, sw=sw, st=st,
                     round_acc=False, map_bytes=map_b, bm=_p(bm), bm_ld=bitmap_ld(bm), bm_rows=bm_rows,
-                    cls=dl().kSlabCls if info[23] else 0, sup_frac=sup_frac)
+                    cls=dl().kSlabCls if info[23] else 0, accb=accb, sup_frac=sup_frac)
     CLS_LEVELS[0] += int(info[23])
     LAST_LEVEL_PLAN.clear()
     LAST_LEVEL_PLAN.update(kernel="slab", rows=int(roff.numel() - 1), used=n_used, sw=sw,
@@ -1828,15 +1843,23 @@ def lane_deal(lib, rows: int) -> None:
     lib.fa_hip_set_lane_deal(int(0 <= TUNING.lane_deal_min_rows <= rows))
 
 
-def dl_plan(S: DeviceLevelState, L: int, F1: int, n_used: int, C: int, lds: int, dev, accb: float = 4.0) -> dict:
+def dl_plan(S: DeviceLevelState, L: int, F1: int, n_used: int, C: int, lds: int, dev, accb: float = 4.0,
+            cnt_accb: float | None = None) -> dict:
     """Device piece plan of a bundle's C candidates (levels.hip fa_hip_dl_plan), queued
     on the stream right after the generator's synchronisation: it depends on the
     candidates only, not on the row layout, so the host's trimming decision runs
-    while it executes.  Returns the plan for dl_count."""
+    while it executes.  accb: the bytes per accumulator the bundle was accepted with;
+    cnt_accb (smaller): taken instead where it moves the slab up to width 16, as the post
+    step does (fa_slab.h slab_acc_upgrade).  Returns the plan for dl_count."""
     st = torch.cuda.current_stream(dev).cuda_stream
     sw, cap = slab_width(n_used, C, lds, accb)
     if sw == 0 or C > cap:
         raise RuntimeError(f"device bundle of {C} candidates over {n_used} items does not fit one pass")
+    if cnt_accb is not None and cnt_accb < accb:
+        sw_c, cap_c, accb_c = ctypes.c_int(sw), ctypes.c_int64(cap), ctypes.c_double(accb)
+        _native.host().fa_slab_acc_upgrade(int(n_used), int(C), float(lds), float(cnt_accb), ctypes.byref(sw_c),
+                                           ctypes.byref(cap_c), ctypes.byref(accb_c))
+        sw, cap, accb = int(sw_c.value), int(cap_c.value), float(accb_c.value)
     item_map = torch.empty(max(F1, 1), dtype=_I32, device=dev)
     rec = torch.empty(12 * C + 12, dtype=_I32, device=dev)
     R = int(S.desc["n"][:L].sum())                   # parent rows of the bundle

@@ -51,6 +51,18 @@ class Tuning:
     dense_min_rows: float = 4.0         # skip the all-zero-prefix test above this many rows per slab
     dl_acc16: bool = True               # packed u16 accumulators in window-by-window levels (unit weights)
     dl_acc16_bundles: bool = False      # ... and in one-pass device bundles
+    # single-writer byte accumulators in one-pass device bundles (unit weights; before
+    # dl_acc16_bundles): four candidates per accumulator word, so a bundle of ~1000 used
+    # items and ~20K candidates counts on 16-word slabs instead of 8-word ones.  0: off;
+    # 1: every bundle is accepted by the slab rule at one byte per candidate and counted in
+    # bytes (the bundling shifts: T10I4D100M 3-5 | 6-12 plus a trim, 40.9 ms against 39.8);
+    # 2: bundled as without the knob, counted in bytes where that moves the bundle's slab
+    # up to width 16 (T10I4D100M levels 3-4: 11.9 -> 9.5 ms, the run 39.95 -> 38.06 ms)
+    dl_acc8_bundles: int = 2
+    # ... from this many rows to count: measured to gain on the 12.5M-row shard (6.21 ->
+    # 6.03 ms) and above, no measurable difference at 100K rows (1.08-1.19 ms either way),
+    # where the bundles stay on the accumulators the rule gave them
+    dl_acc8_min_rows: int = 1 << 20
     mp_window_items: bool = True        # window-by-window levels: each window's slab holds only its own used items
     # window-by-window levels: a window counts only the rows holding >= k of its own items
     # (its items' bitmap compacted to them, count.hip k_win_compact) when the binomial
