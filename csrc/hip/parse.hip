@@ -372,17 +372,31 @@ __global__ __launch_bounds__(1024) void k_scan_small(const int32_t* __restrict__
 // the shard's CSR row offsets); each wave then copies its 64 lines' ids flattened over
 // the lanes (coalesced stores).  hpart (may be null): kHistCap counters per block,
 // added to (one row per workgroup: no atomics).
+// A bad parse (flags[0] & 1, set by k_tparse of this or an earlier region: one stream, so
+// it is complete and visible here) skips the whole launch: k_tparse leaves a thread's line
+// loop at its first bad token, so the dcnt / xcnt / lbase of that thread's later lines are
+// unwritten and must not become scan inputs, gather indices or store counts.  items /
+// extras / off then stay unwritten and hpart untouched (the caller re-parses in dictionary
+// mode, TileParse.finish).  So does a region whose ids would end past items' icap entries
+// (tile_xb[2 ntiles], the running total after this region; a blank line is one id per
+// byte, so a file of mostly blank lines holds more ids than (bytes + 1) / 2): flags[3] |= 2,
+// nothing written, and the caller parses again with room for the ids k_tparse counted.
 __global__ __launch_bounds__(256) void k_tcompact(const int64_t* __restrict__ tile_base,
                                                   const int64_t* __restrict__ tile_xb, int64_t ntiles, int tail,
                                                   const int32_t* __restrict__ dcnt, const int32_t* __restrict__ xcnt,
                                                   const int64_t* __restrict__ lbase,
                                                   const int32_t* __restrict__ scratch,
                                                   const int32_t* __restrict__ xscratch, int32_t* __restrict__ items,
-                                                  int32_t* __restrict__ extras, int64_t xcap,
+                                                  int32_t* __restrict__ extras, int64_t xcap, int64_t icap,
                                                   int64_t* __restrict__ off, unsigned long long* __restrict__ hpart,
                                                   int32_t* __restrict__ flags) {
   __shared__ uint32_t h[kHistCap];
   __shared__ int wsum[2 * 4];
+  if (*reinterpret_cast<const volatile int32_t*>(&flags[0]) & 1) return;     // grid-uniform: nobody sets it here
+  if (tile_xb[2 * ntiles] > icap) {                // the region's last id would land past items
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&flags[3], 2);
+    return;
+  }
   if (hpart)
     for (int b = threadIdx.x; b < kHistCap; b += 256) h[b] = 0u;
   __syncthreads();
@@ -732,12 +746,12 @@ FA_API int fa_hip_scan_small(int k, const int32_t* in, int64_t n, int64_t* out, 
 FA_API int fa_hip_tcompact(const int64_t* tile_base, const int64_t* tile_xb, int64_t ntiles, int tail,
                            const int32_t* dcnt,
                            const int32_t* xcnt, const int64_t* lbase, const int32_t* scratch, const int32_t* xscratch,
-                           int32_t* items, int32_t* extras, int64_t xcap, int64_t* off, int grid,
+                           int32_t* items, int32_t* extras, int64_t xcap, int64_t icap, int64_t* off, int grid,
                            unsigned long long* hpart, int32_t* flags, hipStream_t st) {
   if (ntiles <= 0) return 0;
   if (grid < 1) return 3;
   hipLaunchKernelGGL(k_tcompact, dim3((unsigned)grid), dim3(256), 0, st, tile_base, tile_xb, ntiles, tail, dcnt, xcnt,
-                     lbase, scratch, xscratch, items, extras, xcap, off, hpart, flags);
+                     lbase, scratch, xscratch, items, extras, xcap, icap, off, hpart, flags);
   FA_LAUNCH_RET();
 }
 

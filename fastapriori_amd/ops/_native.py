@@ -141,7 +141,7 @@ _HIP_SIGS = {
     "fa_hip_tline_count": (C.c_int, [vp, i64, i64, vp, vp]),
     "fa_hip_tparse": (C.c_int, [vp, i64, i64, i64, C.c_int, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "fa_hip_scan_small": (C.c_int, [C.c_int, vp, i64, vp, vp, vp]),
-    "fa_hip_tcompact": (C.c_int, [vp, vp, i64, C.c_int, vp, vp, vp, vp, vp, vp, vp, i64, vp, C.c_int, vp, vp, vp]),
+    "fa_hip_tcompact": (C.c_int, [vp, vp, i64, C.c_int, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, C.c_int, vp, vp, vp]),
     "fa_hip_hist_reduce": (C.c_int, [vp, C.c_int, vp, vp]),
     "fa_hip_line_count": (C.c_int, [vp, i64, vp, vp]),
     "fa_hip_line_ends": (C.c_int, [vp, i64, vp, vp, vp]),

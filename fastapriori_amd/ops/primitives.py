@@ -1507,13 +1507,18 @@ class TileParse:
 
     GRID = 1024       # compaction workgroups (rows of the histogram partials): 4 per CU
 
-    def __init__(self, buf: torch.Tensor, n: int, dev, scratch_bytes: int, xcap: int | None = None):
+    def __init__(self, buf: torch.Tensor, n: int, dev, scratch_bytes: int, xcap: int | None = None,
+                 icap: int | None = None):
         self.buf, self.n, self.dev = buf, n, dev
         self.st = _stream(buf)
         self.lib = _native.hip()
         cap = limits().kHistCap
-        tok_cap = (n + 1) // 2 + 1           # tokens are separated: at most (bytes + 1) / 2
-        self.items = torch.empty(tok_cap, dtype=_I32, device=dev)
+        # tokens are separated: at most (bytes + 1) / 2 -- but a blank line is one id ("") per
+        # byte, so a file of mostly blank lines holds more: the compaction then sets flags[3]
+        # and a second parse gets room for all of them (icap, as for the repeats)
+        self.icap = max(int(icap if icap is not None else (n + 1) // 2 + 1), 1)
+        self.items = torch.empty(self.icap, dtype=_I32, device=dev)
+        self.need_items = 0                  # ids counted by finish() (what a second parse needs)
         # repeated ids are rare: a small buffer, and a second parse in the rare file that overflows it
         self.xcap = max(int(xcap if xcap is not None else n // 64 + 4096), 1)
         self.extras = torch.empty(self.xcap, dtype=_I32, device=dev)
@@ -1567,7 +1572,7 @@ class TileParse:
         _native.check(lib.fa_hip_tcompact(_p(tile_base), _p(tile_xb), tiles, int(bool(tail)), _p(dcnt), _p(xcnt),
                                           _p(lbase),
                                           _p(self.scratch), _p(self.xscratch), _p(self.items), _p(self.extras),
-                                          self.xcap, _p(off), grid, _p(self.hpart), _p(self.flags), st),
+                                          self.xcap, self.icap, _p(off), grid, _p(self.hpart), _p(self.flags), st),
                       "fa_hip_tcompact")
         self.offs.append(off)
         self.n_lines += nl
@@ -1575,10 +1580,12 @@ class TileParse:
     def finish(self):
         """(offsets int64 [nl+1], items, extras, vocab size, hist int64 [V] or None), None
         when a token is not canonical numeric, or the number of repeated ids when they
-        overflowed the repeat buffer (parse again with that room).  One readback."""
+        overflowed the repeat buffer or the ids overflowed items (parse again with that
+        room, and with need_items ids of items).  One readback."""
         dev = self.dev
         tail = torch.cat([self.cursor, self.flags.to(_I64)]).cpu().tolist()
         n_items, n_extras, bad, mx, over, xover = (int(v) for v in tail)
+        self.need_items = n_items
         if bad & 1:
             return None
         if xover:
@@ -1606,14 +1613,14 @@ def parse_numeric_device(buf: torch.Tensor, n: int, last_is_term: bool):
         return (torch.zeros(1, dtype=_I64, device=dev), torch.zeros(0, dtype=_I32, device=dev),
                 torch.zeros(0, dtype=_I32, device=dev), 0, None)
     assert buf.numel() >= (n + 63) // 64 * 64 + 64 and buf.dtype == torch.uint8
-    xcap = None
+    xcap = icap = None
     for _ in range(2):
-        tp = TileParse(buf, n, dev, n, xcap)
+        tp = TileParse(buf, n, dev, n, xcap, icap)
         tp.region(0, n, None, tail=not last_is_term)
         got = tp.finish()
         if not isinstance(got, int):
             return got
-        xcap = got                     # every repeated id, counted by the first pass
+        xcap, icap = got, tp.need_items     # every repeated id and every id, counted by the first pass
     raise RuntimeError("device parser: repeat buffer overflow on the second pass")
 
 

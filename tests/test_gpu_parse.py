@@ -2,7 +2,12 @@
 on the same bytes and byte ranges: line splitting (\\n, \\r\\n, lone \\r, no final
 terminator), trim + split, blank lines, duplicate tokens (short lines and lines
 with more distinct tokens than the per-thread LDS column), and the fallback to
-the host parser for non-canonical or non-numeric tokens."""
+the host parser for non-canonical or non-numeric tokens.
+
+The inputs here are mostly random, so which tile, chunk or halo boundary a terminator, a
+line start or a duplicate lands on is left to the generator; test_parse_edges.py places
+them on purpose, calls the device entry points (TileParse regions included) directly and
+compares with a pure-Python reference instead of the host parser."""
 import os
 
 import numpy as np
