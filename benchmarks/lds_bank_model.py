@@ -4,7 +4,9 @@ A piece record's reads are its m prefix rows then its n_ext extension rows, one
 slab row per read position, SW / 2 ds_read_b128 per row.  ds_read_b128 serves a wave
 in four 16-lane groups ({0-3,12-15,20-27}, {4-11,16-19,28-31}, +32); a group's read
 takes one LDS cycle per distinct row that lands on its busiest 16-B slot, where row r
-sits at slot (r * RS) mod 16 (RS = (SW + 2) / 2).  This replays the planner's record
+sits at the slot column of csrc/host/fa_slab.h's layout (slab_row_col: with every row
+padded, --pad-shift 0, (r * RS) mod 16, RS = (SW + 2) / 2; --pad-shift s pads one row in
+2^s, the tail rule's packed layouts).  This replays the planner's record
 order on real candidate sets (a T10I4 shard mined on the CPU) and reports the LDS
 cycles per read relative to conflict-free (1.0) for
 
@@ -16,11 +18,12 @@ cycles per read relative to conflict-free (1.0) for
     in the record travels with its id), so each group's positions are re-scheduled
     step by step with a bipartite matching of lanes to free slots.
 
-Usage: python benchmarks/lds_bank_model.py [--n 1000000] [--sw 8]
+Usage: python benchmarks/lds_bank_model.py [--n 1000000] [--sw 8] [--pad-shift 0]
 """
 from __future__ import annotations
 
 import argparse
+import functools
 import os
 import sys
 from collections import defaultdict
@@ -74,9 +77,9 @@ def pieces(levels, counts1, k: int):
     return out
 
 
-def replay(recs, rs: int, reorder: bool = False, seg_only: int = -1) -> tuple[float, int]:
+def replay(recs, col, reorder: bool = False, seg_only: int = -1) -> tuple[float, int]:
     """LDS cycles / conflict-free cycles over wave steps of 64 records (lane = index);
-    seg_only 0 / 1: prefix / extension reads only."""
+    col: slab row -> 16-B slot column; seg_only 0 / 1: prefix / extension reads only."""
     cyc = base = 0
     for w0 in range(0, len(recs) - 63, 64):
         for g in GROUPS:
@@ -86,17 +89,17 @@ def replay(recs, rs: int, reorder: bool = False, seg_only: int = -1) -> tuple[fl
                 if seg_only >= 0 and si != seg_only:
                     continue
                 n = len(seg[0])
-                steps = schedule(seg, rs) if reorder else [[lane[s] for lane in seg] for s in range(n)]
+                steps = schedule(seg, col) if reorder else [[lane[s] for lane in seg] for s in range(n)]
                 for rows in steps:
                     occ = defaultdict(set)
                     for r in rows:
-                        occ[(r * rs) & 15].add(r)
+                        occ[col(r)].add(r)
                     cyc += max(len(v) for v in occ.values())
                     base += 1
     return cyc / max(base, 1), base
 
 
-def schedule(seg, rs: int):
+def schedule(seg, col):
     """Per step, a maximum matching of lanes to distinct slots among each lane's
     remaining rows (augmenting paths); unmatched lanes take any remaining row."""
     rem = [list(x) for x in seg]
@@ -108,7 +111,7 @@ def schedule(seg, rs: int):
 
         def aug(l, seen):
             for r in rem[l]:
-                s = (r * rs) & 15
+                s = col(r)
                 if s in seen:
                     continue
                 seen.add(s)
@@ -122,7 +125,7 @@ def schedule(seg, rs: int):
             return False
 
         # lanes with the fewest distinct slots first
-        for l in sorted(range(len(rem)), key=lambda l: len({(r * rs) & 15 for r in rem[l]})):
+        for l in sorted(range(len(rem)), key=lambda l: len({col(r) for r in rem[l]})):
             aug(l, set())
         for l in range(len(rem)):
             if pick[l] is None or pick[l] not in rem[l]:
@@ -132,7 +135,7 @@ def schedule(seg, rs: int):
     return steps
 
 
-def deal(recs, rs: int, ws: int = 4, tail: bool = False):
+def deal(recs, col, ws: int = 4, tail: bool = False):
     """levels.hip k_dl_lane_assign: windows of 64 * ws records re-dealt greedily;
     tail: the run's last partial window too (its whole wave steps)."""
     out = list(recs)
@@ -155,13 +158,13 @@ def deal(recs, rs: int, ws: int = 4, tail: bool = False):
                     continue
                 c = 0
                 for p, r in enumerate(rows):
-                    d = st[g][p].get((r * rs) & 15)
+                    d = st[g][p].get(col(r))
                     if d and r not in d:
                         c += sum(d.values())
                 if bc is None or c < bc:
                     best, bc = g, c
             for p, r in enumerate(rows):
-                d = st[best][p].setdefault((r * rs) & 15, {})
+                d = st[best][p].setdefault(col(r), {})
                 d[r] = d.get(r, 0) + 1
             out[b + lane_of[best][fill[best]]] = rec
             fill[best] += 1
@@ -175,8 +178,10 @@ def main():
     ap.add_argument("--sw", type=int, default=8)
     ap.add_argument("--levels", default="3,4")
     ap.add_argument("--t40", action="store_true", help="T40I10 shape (|T| = 40, |I| = 10)")
+    ap.add_argument("--pad-shift", type=int, default=0, help="one 16-B pad slot per 2^s slab rows (0: every row)")
     a = ap.parse_args()
-    rs = (a.sw + 2) // 2
+    from fastapriori_amd.ops import primitives as prim
+    col = functools.lru_cache(maxsize=None)(lambda r: prim.slab_row_col(a.sw, a.pad_shift, r))
     res = mine(a.n, a.ms, *((40.0, 10.0) if a.t40 else (10.0, 4.0)))
     c1 = np.asarray(res.counts[0])
     for k in map(int, a.levels.split(",")):
@@ -189,14 +194,14 @@ def main():
             recs = [([row[x] for x in p], [row[x] for x in e]) for p, e in pcs[ne]]
             if len(recs) < 256:
                 continue
-            r0, nb = replay(recs, rs)
-            dl = deal(recs, rs)
-            r1, _ = replay(dl, rs)
-            p0, e0 = replay(recs, rs, seg_only=0)[0], replay(recs, rs, seg_only=1)[0]
-            p1, e1 = replay(dl, rs, seg_only=0)[0], replay(dl, rs, seg_only=1)[0]
-            r8, _ = replay(deal(recs, rs, 8, True), rs)
-            r16, _ = replay(deal(recs, rs, 16, True), rs)
-            r4t, _ = replay(deal(recs, rs, 4, True), rs)
+            r0, nb = replay(recs, col)
+            dl = deal(recs, col)
+            r1, _ = replay(dl, col)
+            p0, e0 = replay(recs, col, seg_only=0)[0], replay(recs, col, seg_only=1)[0]
+            p1, e1 = replay(dl, col, seg_only=0)[0], replay(dl, col, seg_only=1)[0]
+            r8, _ = replay(deal(recs, col, 8, True), col)
+            r16, _ = replay(deal(recs, col, 16, True), col)
+            r4t, _ = replay(deal(recs, col, 4, True), col)
             print(f"level {k} n_ext {ne}: {len(recs)} records, {nb} group reads: plan {r0:.2f}x (prefix {p0:.2f}x, "
                   f"ext {e0:.2f}x)  deal {r1:.2f}x (prefix {p1:.2f}x, ext {e1:.2f}x)  tail-dealt: ws4 {r4t:.2f}x ws8 {r8:.2f}x  ws16 {r16:.2f}x")
 

@@ -1293,23 +1293,36 @@ __device__ __forceinline__ WordSpan word_span(const int64_t* __restrict__ roff, 
   return WordSpan{roff[min(col0 + lane, ncols)], roff[col0], roff[min(col0 + 64, ncols)]};
 }
 
-template <class Map>
-__device__ __forceinline__ void slab_build_word_span(uint64_t* __restrict__ slab, int swp, int q, const WordSpan& ws,
-                                                     const int32_t* __restrict__ ranks, Map item_map, int h,
-                                                     int nsub, unsigned long long* words, int swz);
+// Where the rows of a tile start, in 8-B words: a slab's rows at pad shift S (fa_slab.h
+// slab_row_off, the one definition of the slab layout), or the dense rows of a bitmap tile
+template <int SW, int S>
+struct SlabRows {
+  __device__ __forceinline__ int operator()(int u) const { return (int)(slab_row_off(SW, S, u) >> 3); }
+  // the row's uint4 slots (ds_read_b128 / ds_write_b128 with immediate offsets inside the row)
+  __device__ __forceinline__ int slot(int u) const { return (int)(slab_row_off(SW, S, u) >> 4); }
+};
+struct TileRows {
+  int stride;
+  __device__ __forceinline__ int operator()(int u) const { return u * stride; }
+};
 
-template <class Map = MapGlobal>
-__device__ __forceinline__ void slab_build_word_m(uint64_t* __restrict__ slab, int swp, int q, int64_t col0,
+template <class Map, class Rows>
+__device__ __forceinline__ void slab_build_word_span(uint64_t* __restrict__ slab, Rows rows, int q, const WordSpan& ws,
+                                                     const int32_t* __restrict__ ranks, Map item_map, int h,
+                                                     int nsub, unsigned long long* words);
+
+template <class Map, class Rows>
+__device__ __forceinline__ void slab_build_word_m(uint64_t* __restrict__ slab, Rows rows, int q, int64_t col0,
                                                   int64_t ncols, const int64_t* __restrict__ roff,
                                                   const int32_t* __restrict__ ranks, Map item_map, int h,
-                                                  int nsub, unsigned long long* words, int swz = 0) {
-  slab_build_word_span(slab, swp, q, word_span(roff, col0, ncols), ranks, item_map, h, nsub, words, swz);
+                                                  int nsub, unsigned long long* words) {
+  slab_build_word_span(slab, rows, q, word_span(roff, col0, ncols), ranks, item_map, h, nsub, words);
 }
 
-template <class Map>
-__device__ __forceinline__ void slab_build_word_span(uint64_t* __restrict__ slab, int swp, int q, const WordSpan& ws,
+template <class Map, class Rows>
+__device__ __forceinline__ void slab_build_word_span(uint64_t* __restrict__ slab, Rows rows, int q, const WordSpan& ws,
                                                      const int32_t* __restrict__ ranks, Map item_map, int h,
-                                                     int nsub, unsigned long long* words, int swz) {
+                                                     int nsub, unsigned long long* words) {
   const int lane = threadIdx.x & 63;
   const int64_t st = ws.st, base = ws.base, end = ws.end;
   const int srel = (int)(st - base);
@@ -1344,30 +1357,21 @@ __device__ __forceinline__ void slab_build_word_span(uint64_t* __restrict__ slab
     for (int u = 0; u < U; ++u) {
       const int l = cs + __popcll(S[u] & le) - 1;
       const int uu = r[u] >= 0 ? item_map(r[u]) : -1;
-      if (uu >= 0) atomicOr((unsigned long long*)(slab + (size_t)uu * swp + (q ^ ((uu << 2) & swz))), 1ull << l);
+      if (uu >= 0) atomicOr((unsigned long long*)(slab + rows(uu) + q), 1ull << l);
       cs += __popcll(S[u]);
     }
   }
-}
-
-__device__ __forceinline__ void slab_build_word(uint64_t* __restrict__ slab, int swp, int q, int64_t col0,
-                                                int64_t ncols, const int64_t* __restrict__ roff,
-                                                const int32_t* __restrict__ ranks,
-                                                const int32_t* __restrict__ item_map, int h, int nsub,
-                                                unsigned long long* words, int swz = 0) {
-  slab_build_word_m(slab, swp, q, col0, ncols, roff, ranks, MapGlobal{item_map}, h, nsub, words, swz);
 }
 
 // Multi-pass levels copy the slab tile of every used item from the
 // materialised bitmap.  A plain strided loop (load, store, next) pays one global
 // round trip per 16 B a thread copies (~8-10 per slab at 1024 threads);
 // here every thread issues all its loads (after one batched load of the
-// bitmap row ids) before its first LDS store.  ROWW: LDS row stride in words;
-// kSwz: an XOR of the word slot by ((u << 2) & (SW - 4)) (rotated row layouts).
+// bitmap row ids) before its first LDS store.  S: the slab rows' pad shift (SlabRows).
 // ld > 0: a row-major bitmap of row stride ld; ld < 0: the 8-word block layout of
 // block stride -ld (BmView: the Gram's bitmap, reused by the levels after it; slab
 // starts and word pairs stay inside one block).
-template <int SW, int ROWW, bool kSwz>
+template <int SW, int S>
 __device__ __forceinline__ void slab_copy_bm(uint4* lds4, int n_used, const uint64_t* __restrict__ bm, int64_t Wp,
                                              const int32_t* __restrict__ bm_rows, int64_t w0, int64_t W) {
   constexpr int QW = SW / 2;                 // uint4 per row
@@ -1396,8 +1400,7 @@ __device__ __forceinline__ void slab_copy_bm(uint4* lds4, int n_used, const uint
       const int i = base + (int)threadIdx.x + k * kSlabThreads;
       if (i < total) {
         const int u = i / QW, q = i % QW;
-        const int qq = kSwz ? (q ^ (((u << 2) & (SW - 4)) >> 1)) : q;
-        lds4[(size_t)u * (ROWW / 2) + qq] = v[k];
+        lds4[SlabRows<SW, S>{}.slot(u) + q] = v[k];
       }
     }
   }
@@ -1450,7 +1453,7 @@ __device__ __forceinline__ int u16_at(const int4& v, int k) {
   return (k & 1) ? (int)((uint32_t)w >> 16) : (w & 0xFFFF);
 }
 
-template <int SW, bool kWeighted, int kBuild, bool kCls = false, int kAccB = 4>
+template <int SW, bool kWeighted, int kBuild, bool kCls = false, int kAccB = 4, int kPad = 0>
 __global__ __launch_bounds__(kSlabThreads) void k_count_slab_rec(
     const int64_t* __restrict__ roff, const int32_t* __restrict__ ranks, const int32_t* __restrict__ src,
     int64_t ncols, const int32_t* __restrict__ item_map, int F1, int n_used, const int32_t* __restrict__ gpre,
@@ -1461,8 +1464,13 @@ __global__ __launch_bounds__(kSlabThreads) void k_count_slab_rec(
   const int G = g_dev ? *g_dev : G_arg;
   extern __shared__ uint4 lds4[];
   __shared__ unsigned long long build_words[kSlabThreads / 64 * 2];
-  constexpr int SWP = SW + 2;                       // row stride: odd number of 16-B slots
-  constexpr int RS = SWP / 2;
+  // the rows' places (fa_slab.h): kPad = 0 pads every row (an odd number of 16-B slots per
+  // row), kPad = s one row in 2^s.  A template parameter: the reads inside a row keep
+  // immediate offsets, a row's base costs one shift-and-add more than the multiply alone.
+  static_assert(kPad >= 0 && kPad <= kSlabPadMax, "pad shift");
+  constexpr SlabRows<SW, kPad> rows{};
+  auto row4 = [&](int u) { return lds4 + rows.slot(u); };
+  const int slab_slots = (int)(slab_rows_bytes(SW, kPad, n_used) >> 4);   // uint4 of n_used rows
   uint64_t* slab = reinterpret_cast<uint64_t*>(lds4);
   // kAccB = 2 (flags & kSlabFlagAcc16): two u16 counters per accumulator word (unit weights; twice the
   // candidates per accumulator pass), drained into the u32 global counts before they can
@@ -1474,7 +1482,7 @@ __global__ __launch_bounds__(kSlabThreads) void k_count_slab_rec(
   constexpr bool acc8 = !kWeighted && kAccB == 1;
   const int nacc = acc16 ? (C + 1) >> 1 : acc8 ? (C + 3) >> 2 : C;
   constexpr int kFlush16 = 65535 / (SW * 64);
-  uint32_t* acc = reinterpret_cast<uint32_t*>(slab + (size_t)n_used * SWP);
+  uint32_t* acc = reinterpret_cast<uint32_t*>(lds4 + slab_slots);   // behind the last row's footprint
   uint8_t* acc8p = reinterpret_cast<uint8_t*>(acc);
   uint16_t* smap = reinterpret_cast<uint16_t*>(acc + ((nacc + 3) & ~3));
   const bool map_lds = kBuild == kBuildContig && F1 <= kMapLdsMax;
@@ -1499,7 +1507,7 @@ __global__ __launch_bounds__(kSlabThreads) void k_count_slab_rec(
   if (g0 < G) { ra = rec[3 * g0]; rb = rec[3 * g0 + 1]; rc = rec[3 * g0 + 2]; }
 
   auto and_row = [&](uint4 (&p)[SW / 2], int u) {
-    const uint4* r = lds4 + (size_t)u * RS;
+    const uint4* r = row4(u);
 #pragma unroll
     for (int q = 0; q < SW / 2; ++q) {
       const uint4 v = r[q];
@@ -1510,8 +1518,8 @@ __global__ __launch_bounds__(kSlabThreads) void k_count_slab_rec(
   // prefix ANDs were ~60 % of the counting VALU of the deep bundles (m ~ 5, 1-2
   // extensions per piece)
   auto and_row2 = [&](uint4 (&p)[SW / 2], int u, int w) {
-    const uint4* r = lds4 + (size_t)u * RS;
-    const uint4* t = lds4 + (size_t)w * RS;
+    const uint4* r = row4(u);
+    const uint4* t = row4(w);
 #pragma unroll
     for (int q = 0; q < SW / 2; ++q) {
       const uint4 v = r[q], x = t[q];
@@ -1584,11 +1592,11 @@ __global__ __launch_bounds__(kSlabThreads) void k_count_slab_rec(
       nsl = 1;
     }
     if (kBuild == kBuildBM) {
-      slab_copy_bm<SW, SWP, false>(lds4, n_used, bm, Wp, bm_rows, w0, W);
+      slab_copy_bm<SW, kPad>(lds4, n_used, bm, Wp, bm_rows, w0, W);
     } else {
       {
         const uint4 z = make_uint4(0, 0, 0, 0);
-        for (int i = threadIdx.x; i < n_used * RS; i += blockDim.x) lds4[i] = z;
+        for (int i = threadIdx.x; i < slab_slots; i += blockDim.x) lds4[i] = z;
       }
       __syncthreads();
       if (kBuild == kBuildContig) {
@@ -1600,19 +1608,19 @@ __global__ __launch_bounds__(kSlabThreads) void k_count_slab_rec(
           const int q = wv / NSUB;
           if ((w0 + q) * 64 < ncols) {
             if (map_lds)
-              slab_build_word_span(slab, SWP, q, span, ranks, MapLds{smap}, wv % NSUB, NSUB, build_words + wv * 2, 0);
+              slab_build_word_span(slab, rows, q, span, ranks, MapLds{smap}, wv % NSUB, NSUB, build_words + wv * 2);
             else
-              slab_build_word_span(slab, SWP, q, span, ranks, MapGlobal{item_map}, wv % NSUB, NSUB,
-                                   build_words + wv * 2, 0);
+              slab_build_word_span(slab, rows, q, span, ranks, MapGlobal{item_map}, wv % NSUB, NSUB,
+                                   build_words + wv * 2);
           }
         } else {
           for (int q = wv / NSUB; q < SW; q += NW / NSUB) {
             if ((w0 + q) * 64 >= ncols) continue;
             if (map_lds)
-              slab_build_word_m(slab, SWP, q, (w0 + q) * 64, ncols, roff, ranks, MapLds{smap}, wv % NSUB, NSUB,
+              slab_build_word_m(slab, rows, q, (w0 + q) * 64, ncols, roff, ranks, MapLds{smap}, wv % NSUB, NSUB,
                                 build_words + wv * 2);
             else
-              slab_build_word_m(slab, SWP, q, (w0 + q) * 64, ncols, roff, ranks, MapGlobal{item_map}, wv % NSUB,
+              slab_build_word_m(slab, rows, q, (w0 + q) * 64, ncols, roff, ranks, MapGlobal{item_map}, wv % NSUB,
                                 NSUB, build_words + wv * 2);
           }
         }
@@ -1627,7 +1635,7 @@ __global__ __launch_bounds__(kSlabThreads) void k_count_slab_rec(
           uint64_t* base = slab + (j >> 6);
           for (int64_t r = roff[row], r1 = roff[row + 1]; r < r1; ++r) {
             const int uu = item_map[ranks[r]];
-            if (uu >= 0) atomicOr((unsigned long long*)(base + (size_t)uu * SWP), bit);
+            if (uu >= 0) atomicOr((unsigned long long*)(base + rows(uu)), bit);
           }
         }
       }
@@ -1649,7 +1657,7 @@ __global__ __launch_bounds__(kSlabThreads) void k_count_slab_rec(
       if constexpr (kCls) {
         const int fl = (ra.y >> 17) & 3;
         if (!(fl & 1)) {
-          const uint4* r0 = lds4 + (size_t)(ra.z & 0xFFFF) * RS;
+          const uint4* r0 = row4(ra.z & 0xFFFF);
 #pragma unroll
           for (int q = 0; q < SW / 2; ++q) qv[q] = r0[q];
           and_prefix(qv, 1, m - 1);
@@ -1657,7 +1665,7 @@ __global__ __launch_bounds__(kSlabThreads) void k_count_slab_rec(
         if (!(fl & 2)) {
           // the last prefix id rides in the record's bits 19-31 (a runtime u16_at index
           // would put the record in scratch memory)
-          const uint4* rl = lds4 + (size_t)((uint32_t)ra.y >> 19) * RS;
+          const uint4* rl = row4((int)((uint32_t)ra.y >> 19));
 #pragma unroll
           for (int q = 0; q < SW / 2; ++q) {
             const uint4 v = rl[q];
@@ -1666,7 +1674,7 @@ __global__ __launch_bounds__(kSlabThreads) void k_count_slab_rec(
         }
       } else {
       {
-        const uint4* r0 = lds4 + (size_t)(ra.z & 0xFFFF) * RS;
+        const uint4* r0 = row4(ra.z & 0xFFFF);
 #pragma unroll
         for (int q = 0; q < SW / 2; ++q) p[q] = r0[q];
       }
@@ -1698,7 +1706,7 @@ __global__ __launch_bounds__(kSlabThreads) void k_count_slab_rec(
 #pragma unroll
           for (int x = 0; x < UE; ++x) {
             s[x] = 0;
-            r[x] = lds4 + (size_t)u16_at(rb, k + x < n_ext ? k + x : k) * RS;
+            r[x] = row4(u16_at(rb, k + x < n_ext ? k + x : k));
           }
 #pragma unroll
           for (int q = 0; q < SW / 2; ++q) {
@@ -1757,8 +1765,8 @@ __global__ __launch_bounds__(kBwThreads) void k_build_bitmaps_w(const int64_t* _
   for (int q = wv / nsub; q < WT; q += NW / nsub) {
     const int64_t col0 = ((int64_t)blockIdx.x * WT + q) * 64;
     if (col0 < ncols)
-      slab_build_word_span(btile, WT, q, word_span(roff, col0, ncols), ranks, map, wv % nsub, nsub, bwords + wv * 2,
-                           0);
+      slab_build_word_span(btile, TileRows{WT}, q, word_span(roff, col0, ncols), ranks, map, wv % nsub, nsub,
+                           bwords + wv * 2);
   }
   __syncthreads();
   const int64_t w0 = (int64_t)blockIdx.x * WT;
@@ -2037,6 +2045,9 @@ FA_API int fa_hip_win_compact(const uint64_t* bm, int64_t ld, const int32_t* row
 // accumulators (unit weights: half the LDS per candidate, drained every 65535 / (SW * 64)
 // slabs).  fa_slab.h kSlabAcc8: single-writer byte accumulators (unit weights: a quarter of
 // the LDS per candidate, no drain).  Weighted rows count into u32 whatever the mode asks.
+// sw: the slab layout (fa_slab.h slab_layout): the bare width pads every row; a pad shift
+// of 1 .. kSlabPadMax (widths 8 and 16, plain records: the class layout's flags are hints
+// and are dropped) pads one row in 2, 4 or 8.  Returns 1 for a layout with no kernel.
 // Test hook: at most this many workgroups per slab count (0: no cap).  One workgroup
 // then walks every slab, so the packed-u16 accumulators' mid-run drain (every
 // kFlush16 slabs) runs on inputs of a few hundred thousand rows.
@@ -2055,19 +2066,22 @@ FA_API int fa_hip_set_piece_part(int part, int nparts) {
 
 FA_API int fa_hip_count_slab_rec_cls(const int64_t* roff, const int32_t* ranks, const int32_t* src, int64_t ncols,
                                      const int32_t* item_map, int F1, int n_used, const int32_t* gpre,
-                                     const void* rec, int G, int C, const int32_t* wword, uint32_t* out, int sw,
+                                     const void* rec, int G, int C, const int32_t* wword, uint32_t* out, int layout,
                                      int n_wg, const uint64_t* bm, int64_t Wp, hipStream_t st,
                                      const int32_t* bm_rows, const int32_t* g_dev, int cls) {
   if ((G <= 0 && !g_dev) || C <= 0 || ncols <= 0) return 0;
   // the class-layout flags name a thread's previous piece in the undivided plan: with the
   // pieces divided among ranks the plain kernel recomputes every prefix instead
-  if (g_piece_nparts > 1) cls &= ~kSlabCls;
+  const int sw = slab_layout_sw(layout), pad = slab_layout_pad(layout);
+  if (g_piece_nparts > 1 || pad > 0) cls &= ~kSlabCls;
   // fa_slab.h: u32, two u16 (kSlabAcc16) or four bytes (kSlabAcc8) per accumulator word
   const int accb = slab_mode_acc_bytes(cls, wword != nullptr);
   const bool acc16 = accb == 2;
   const int64_t n_acc = slab_acc_count(C, accb);
   const bool contig = !bm && !src;
-  const size_t lds = (size_t)slab_kernel_lds(n_used, sw, slab_acc_words(n_acc), contig ? slab_map_lds(F1) : 0);
+  if (pad > kSlabPadMax || n_used < 1) return 1;
+  const size_t lds =
+      (size_t)slab_kernel_lds_pack(n_used, sw, pad, slab_acc_words(n_acc), contig ? slab_map_lds(F1) : 0);
   if (lds > 160 * 1024 - 256) return 3;             // static build_words scratch
   if (g_slab_max_wg > 0) n_wg = std::min(n_wg, g_slab_max_wg);
   using KernT = void (*)(const int64_t*, const int32_t*, const int32_t*, int64_t, const int32_t*, int, int,
@@ -2083,7 +2097,7 @@ FA_API int fa_hip_count_slab_rec_cls(const int64_t* roff, const int32_t* ranks, 
                                : accb == 2 ? (KernT)k_count_slab_rec<S, false, B, false, 2>            \
                                            : (KernT)k_count_slab_rec<S, false, B, false, 4>);
 #define FA_REC_CASE(S)                                    \
-  if (sw == S) {                                          \
+  if (sw == S && pad == 0) {                              \
     if (bm) { FA_REC_MODE(S, kBuildBM) }                  \
     else if (src) { FA_REC_MODE(S, kBuildCols) }          \
     else { FA_REC_MODE(S, kBuildContig) }                 \
@@ -2094,6 +2108,22 @@ FA_API int fa_hip_count_slab_rec_cls(const int64_t* roff, const int32_t* ranks, 
   FA_REC_CASE(32)
 #undef FA_REC_CASE
 #undef FA_REC_MODE
+  // thinner padding: plain records only
+#define FA_REC_PMODE(S, B, P)                                                            \
+  kern = wword ? (KernT)k_count_slab_rec<S, true, B, false, 4, P>                        \
+         : accb == 1 ? (KernT)k_count_slab_rec<S, false, B, false, 1, P>                 \
+         : accb == 2 ? (KernT)k_count_slab_rec<S, false, B, false, 2, P>                 \
+                     : (KernT)k_count_slab_rec<S, false, B, false, 4, P>;
+#define FA_REC_PCASE(S, P)                                \
+  if (sw == S && pad == P) {                              \
+    if (bm) { FA_REC_PMODE(S, kBuildBM, P) }              \
+    else if (src) { FA_REC_PMODE(S, kBuildCols, P) }      \
+    else { FA_REC_PMODE(S, kBuildContig, P) }             \
+  }
+  FA_REC_PCASE(8, 1) FA_REC_PCASE(8, 2) FA_REC_PCASE(8, 3)
+  FA_REC_PCASE(16, 1) FA_REC_PCASE(16, 2) FA_REC_PCASE(16, 3)
+#undef FA_REC_PCASE
+#undef FA_REC_PMODE
   if (!kern) return 1;
   (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   const int flags = ((cls & kSlabDense) ? kSlabFlagDense : 0) | (acc16 ? kSlabFlagAcc16 : 0) |

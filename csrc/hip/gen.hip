@@ -849,17 +849,21 @@ __global__ __launch_bounds__(64) void k_dl_post0(long long* __restrict__ c, doub
 }
 
 // acceptance of speculative level l >= 1 (same rule as k_agd_scan_decide, with the
-// exact one-pass test total + C <= slab capacity(n_used, total + C))
+// exact one-pass test total + C <= slab capacity(n_used, total + C)).  accb_pack > 0 (the
+// tail rule, fa_slab.h): a level also joins while the total fits one packed pass at width
+// 16 with accb_pack bytes per accumulator; dl_post keeps such a bundle whole only where
+// it ends the run, and otherwise cuts it back to the levels the first test accepts.
 __global__ __launch_bounds__(1024) void k_dl_decide(const int32_t* __restrict__ cnt, int64_t* __restrict__ off,
                                                      long long* __restrict__ c, int l, double growth, int64_t c_bound,
-                                                     double lds, double accb) {
+                                                     double lds, double accb, double accb_pack) {
   if (c[kDlStop]) return;
   int64_t g = 0;
   const int64_t C = agd_block_scan<true>(cnt, off, c[kDlNl + l], &g);
   if (threadIdx.x != 0) return;
   const int64_t total = c[kDlTotal], last = c[kDlLastC];
   if (C == 0 || (double)C > growth * (double)last || C > c_bound ||
-      total + C > slab_cap(c[kDlNUsed], total + C, lds, accb)) {
+      (total + C > slab_cap(c[kDlNUsed], total + C, lds, accb) &&
+       !(accb_pack > 0.0 && slab_pack_fits(c[kDlNUsed], total + C, lds, accb_pack)))) {
     c[kDlStop] = 1;
     // no candidates even from the previous level's candidates (a superset of its
     // frequent rows): the mining ends with this bundle (the host skips the next one)
@@ -1010,12 +1014,67 @@ FA_API int fa_hip_dl_level0(const int32_t* P0, const long long* n_src, int64_t n
 // Returns 0 (ctl_host[kDlLevels] = accepted levels incl. level 0), 5 (ws too small:
 // info[0] = bytes needed) or 7.  post (optional, host DlPost, fa_dl.h): the bundle's
 // plan, trimming decision and count, queued right after the synchronisation.
-static void dl_post(DlPost* P, const DlDesc* desc, int L, long long* ctl, const long long* ch, int F1,
-                    double accb_rule, hipStream_t st) {
+// The tail rule (fa_slab.h) after a chain run with accb_pack > 0 (k_dl_decide).  Lp: the levels
+// the unpacked rule accepts (slab_tail_cut).  Lp == L: the rule changes nothing about the
+// bundle.  Otherwise the whole bundle is counted in one packed pass (dl_tail returns true:
+// *sw, *cap, *pad) where it ends the run -- the chain found no further candidates
+// (kDlEmpty), or --max-level cuts the mining at its last level (g_tail_levels) -- and the
+// plan and count buffers hold it.  Everywhere else the bundle is cut back to Lp levels
+// (dl_tail_cut), exactly the levels a chain without the rule accepts: moving a split instead
+// of removing it measured slower.
+//
+// The rule's inputs, set by fastapriori_amd.ops.primitives before each bundle is generated
+// (TUNING.dl_tail_bundle): accb_pack, the bytes per accumulator of a packed pass (0: the rule
+// is off), and end_levels > 0, the levels of a bundle that reaches --max-level.  They decide
+// which levels share a bundle, so every rank sets the same values.  They apply to
+// fa_hip_dl_more with a post step, unit weights and the rank map in LDS; P->sw reports the
+// layout taken (slab_layout).  (Beside the lane deal's and the piece division's setters, not in
+// DlPost: its 33 fields are a pinned interface, tests/test_dl_layout.py.)
+static double g_tail_accb = 0.0;
+static int g_tail_levels = 0;
+FA_API void fa_hip_set_dl_tail(double accb_pack, int end_levels) {
+  g_tail_accb = accb_pack;
+  g_tail_levels = end_levels;
+}
+
+// The bundle cut back to its first Lp levels: *L and the host mirror of the control block
+// (Python reads the bundle from it), as a chain that stopped there leaves them
+static void dl_tail_cut(const DlDesc* desc, int* L, int Lp, long long* ch) {
+  int64_t total = 0;
+  for (int l = 0; l < Lp; ++l) total += desc[l].C;
+  ch[kDlLevels] = Lp;
+  ch[kDlTotal] = total;
+  ch[kDlLastC] = desc[Lp - 1].C;
+  ch[kDlEmpty] = 0;                                // levels follow this bundle
+  *L = Lp;
+}
+
+static bool dl_tail(const DlPost* P, const DlDesc* desc, int* L, long long* ch, double accb_rule, double accb_pack,
+                    double lds, int* Lp_out, int* sw, int64_t* cap, int* pad) {
+  int64_t Cl[kDlMaxL], C = 0, R = 0;
+  for (int l = 0; l < *L; ++l) { Cl[l] = desc[l].C; C += desc[l].C; R += desc[l].n; }
+  const int64_t n_used = ch[kDlNUsed];
+  const int Lp = *Lp_out = slab_tail_cut(Cl, *L, n_used, lds, accb_rule);
+  if (Lp == *L) return false;
+  const bool ends = ch[kDlEmpty] || (g_tail_levels > 0 && *L == g_tail_levels);
+  if (ends && C <= P->rec_cap && C <= P->out_cap && 8 * ((R + 255) / 256) <= P->part_cap &&
+      slab_pack_width(n_used, C, lds, accb_pack, cap, pad) == 16 && C <= *cap) {
+    *sw = 16;
+    return true;
+  }
+  dl_tail_cut(desc, L, Lp, ch);
+  return false;
+}
+
+static void dl_post(DlPost* P, const DlDesc* desc, int L, long long* ctl, long long* ch, int F1,
+                    double accb_rule, double accb_pack, double lds, hipStream_t st) {
   P->done = 0;
   if (ch[kDlStop] && ch[kDlLevels] == 0) return;   // nothing accepted
   // bound error, multi-pass level, end of mining
   if (ch[kDlOverBound] || ch[kDlMulti] || ch[kDlEnd] || L < 1) return;
+  int64_t cap = 0;
+  int sw = 0, pad = 0, Lp = L;
+  const bool packed = accb_pack > 0.0 && dl_tail(P, desc, &L, ch, accb_rule, accb_pack, lds, &Lp, &sw, &cap, &pad);
   int64_t C = 0, R = 0;
   for (int l = 0; l < L; ++l) { C += desc[l].C; R += desc[l].n; }
   const int64_t n_used = ch[kDlNUsed];
@@ -1024,17 +1083,24 @@ static void dl_post(DlPost* P, const DlDesc* desc, int L, long long* ctl, const 
   // slab width (fa_slab.h), one accumulator pass
   // (accb_rule: the bytes per accumulator the bundle was accepted with; P->accb, when
   // smaller, the accumulators the count may take where they move the slab up to width 16)
-  int64_t cap = 0;
-  int sw = slab_width(n_used, C, P->lds_budget, accb_rule, &cap);
-  if (sw == 0 || C > cap) return;
   double accb = accb_rule;
-  if (!P->wword) slab_acc_upgrade(n_used, C, P->lds_budget, P->accb, &sw, &cap, &accb);
+  if (packed) {
+    accb = accb_pack;
+  } else {
+    sw = slab_width(n_used, C, P->lds_budget, accb_rule, &cap);
+    if (sw == 0 || C > cap) return;
+    if (!P->wword) slab_acc_upgrade(n_used, C, P->lds_budget, P->accb, &sw, &cap, &accb);
+  }
   P->accb = accb;                                  // what the count uses (dl_plan_from_post)
-  if (fa_hip_dl_plan(desc, L, ctl, F1, P->item_map, P->rec, C, P->part, P->part_cap, P->gpre, P->gpre_cap, sw,
-                     st) != 0)
-    return;                                        // (e.g. long prefixes past gpre_cap: the caller plans)
+  if (fa_hip_dl_plan(desc, L, ctl, F1, P->item_map, P->rec, C, P->part, P->part_cap, P->gpre, P->gpre_cap,
+                     slab_layout(sw, pad), st) != 0) {
+    // (e.g. long prefixes past gpre_cap: the caller plans -- a packed bundle cut back to the
+    // levels the unpacked rule accepts, which the caller's planner knows)
+    if (packed) dl_tail_cut(desc, &L, Lp, ch);
+    return;
+  }
   (void)hipMemsetAsync(P->out, 0, 4 * (size_t)C, st);
-  P->sw = sw;
+  P->sw = slab_layout(sw, pad);
   P->cap = cap;
   P->done = 1;
   // trimming before level k: the rows that keep >= k of the bundle's items
@@ -1062,9 +1128,10 @@ static void dl_post(DlPost* P, const DlDesc* desc, int L, long long* ctl, const 
   const bool weighted = P->wword != nullptr;
   const int64_t nacc = slab_acc_count(C, slab_acc_bytes(P->accb, weighted));
   P->n_wg = slab_workgroups(nslabs, (int64_t)P->lds_kernel,
-                            slab_kernel_lds(n_used, sw, slab_acc_words(nacc), slab_map_lds(F1)));
+                            slab_kernel_lds_pack(n_used, sw, pad, slab_acc_words(nacc), slab_map_lds(F1)));
   if (fa_hip_count_slab_rec_cls(P->roff, P->ranks, P->src, P->ncols, P->item_map, F1, (int)n_used, P->gpre, P->rec,
-                                0, (int)C, P->wword, P->out, sw, (int)P->n_wg, nullptr, 0, st, nullptr,
+                                0, (int)C, P->wword, P->out, slab_layout(sw, pad), (int)P->n_wg, nullptr, 0, st,
+                                nullptr,
                                 reinterpret_cast<const int32_t*>(ctl + kDlPiecesI32),
                                 slab_acc_mode(P->accb, weighted)) != 0)
     return;
@@ -1081,6 +1148,9 @@ FA_API int fa_hip_dl_more(int F1, void* ws, int64_t ws_bytes, int64_t ws_used, l
   char* w = w0 + ws_used;
   const int LM = std::min(max_levels, kDlMaxLevels);
   const int64_t acc_max = (int64_t)(lds / accb);
+  // the tail rule (fa_hip_set_dl_tail): unit weights, the rank map in LDS
+  const DlPost* const tp = static_cast<const DlPost*>(post);
+  const double accb_pack = tp && !tp->wword && F1 <= kSlabMapMaxF1 ? g_tail_accb : 0.0;
   int64_t nb = n1_bound;
   int m = (int)desc[0].m + 1;
   const int32_t* P = reinterpret_cast<const int32_t*>((intptr_t)desc[0].rows);
@@ -1146,7 +1216,7 @@ FA_API int fa_hip_dl_more(int F1, void* ws, int64_t ws_bytes, int64_t ws_used, l
 #define FA_DLR_EMIT(N) FA_DLR(true, N)
       FA_AG_NWL_SWITCH(nw, FA_DLR_CNT)
       hipLaunchKernelGGL(k_dl_decide, dim3(1), dim3(1024), 0, st, lv[l].cnt, lv[l].off, ctl, l, growth, cb, lds,
-                         accb);
+                         accb, accb_pack);
       FA_AG_NWL_SWITCH(nw, FA_DLR_EMIT)
 #undef FA_DLR_EMIT
 #undef FA_DLR_CNT
@@ -1189,6 +1259,6 @@ FA_API int fa_hip_dl_more(int F1, void* ws, int64_t ws_bytes, int64_t ws_used, l
     d.base = desc[l - 1].base + desc[l - 1].C;
   }
   info[0] = w - w0;
-  if (post) dl_post(static_cast<DlPost*>(post), desc, L, ctl, ctl_host, F1, accb, st);
+  if (post) dl_post(static_cast<DlPost*>(post), desc, L, ctl, ctl_host, F1, accb, accb_pack, lds, st);
   FA_LAUNCH_RET();
 }

@@ -21,6 +21,7 @@
 // record; longer ones (up to kDlMaxM) are written to gpre, the record pointing there.
 #include "fa_hip.h"
 #include "../host/fa_dl.h"
+#include "../host/fa_slab.h"
 
 namespace fa {
 
@@ -258,8 +259,10 @@ __global__ __launch_bounds__(64) void k_la_qsum_probe(int* out) { out[threadIdx.
 // alone reads and writes the state of group g at its positions, so the greedy steps
 // need no LDS barrier (a wave's LDS operations complete in order); the next record's
 // rows are read ahead, and the cost sum crosses rows by lane swaps (la_qsum).
+// A row's slot is its 16-B column in the slab layout (fa_slab.h slab_row_col; sw, pad: the
+// count's width and pad shift).
 __global__ __launch_bounds__(64) void k_dl_lane_assign(int4* __restrict__ rec, const long long* __restrict__ c,
-                                                       int rs) {
+                                                       int sw, int pad) {
   constexpr int NW = 64 * kLaWs, NG = 4 * kLaWs;
   constexpr int kPq = kLaMaxPos / 4;             // positions per lane
   __shared__ int4 win[3 * NW];
@@ -307,7 +310,7 @@ __global__ __launch_bounds__(64) void k_dl_lane_assign(int4* __restrict__ rec, c
       const int pos = q + 4 * t;
       const bool ok = pos < R;
       const int pc = ok ? pos : 0;
-      const uint32_t sv = st[pc][(rr[t] * rs) & 15][g];
+      const uint32_t sv = st[pc][slab_row_col(sw, pad, rr[t])][g];
       const int rv = (int)rws[i1][pc];
       w[t] = ok ? sv : 0xFFFFu;
       rn[t] = ok ? rv : -1;
@@ -329,7 +332,7 @@ __global__ __launch_bounds__(64) void k_dl_lane_assign(int4* __restrict__ rec, c
         // seen there, one more row there, or unchanged (the same row broadcasts)
         const int o = (int)(w[t] & 0xFFFF);
         const uint32_t nv = o == 0xFFFF ? ((uint32_t)rr[t] | (1u << 16)) : (o != rr[t] ? w[t] + (1u << 16) : w[t]);
-        if (pos < R) st[pos][(rr[t] * rs) & 15][g] = nv;
+        if (pos < R) st[pos][slab_row_col(sw, pad, rr[t])][g] = nv;
       }
       if (q == 0) {
         // the fill-th lane of ds_read_b128 group g % 4 in wave step g / 4
@@ -531,6 +534,8 @@ FA_API void fa_hip_set_lane_deal(int on) { g_lane_on = on; }
 // scratch of 8 per 256 parent rows (part_cap); gpre: int32 [gpre_cap] out, the prefix
 // slab rows of levels with prefixes past kDlInline ids (fa_hip_dl_gpre_need).  The
 // piece count lands in ctl[kDlPieces] (int32 copy at ctl + kDlPiecesI32, the count kernel's G).
+// sw: the count's slab layout (fa_slab.h slab_layout: the width, pad shift 0, or width and
+// shift), which the lane deal's slot columns follow; 0: no deal.
 FA_API int fa_hip_dl_plan(const DlDesc* desc, int L, long long* ctl, int F1, int32_t* item_map, void* rec,
                           int64_t max_pieces, int32_t* part, int64_t part_cap, int32_t* gpre, int64_t gpre_cap,
                           int sw, hipStream_t st) {
@@ -576,7 +581,7 @@ FA_API int fa_hip_dl_plan_window_bits(const DlDesc* desc, int L, long long* ctl,
     const int64_t nwin = (D.w1 - D.w0) / (64 * kLaWs);   // pieces <= candidates of the window
     if (nwin > 0)
       hipLaunchKernelGGL(k_dl_lane_assign, dim3((unsigned)nwin), dim3(64), 0, st, static_cast<int4*>(rec), ctl,
-                         (sw + 2) / 2);
+                         slab_layout_sw(sw), slab_layout_pad(sw));
   }
   FA_LAUNCH_RET();
 }

@@ -7,7 +7,10 @@
 // does the bundle fit one pass -- and answers it here: plan.cpp (host planner),
 // gen.hip (host-loop chain, device chain, the bundle post step), count.hip (the
 // launcher's footprint check) and, through libfa_host.so's fa_slab_* exports
-// (plan.cpp), fastapriori_amd.ops.primitives.
+// (plan.cpp), fastapriori_amd.ops.primitives.  The rows' layout inside the slab (where row
+// u starts, which 16-B slot column it falls on) is defined here too, for the kernel's builds
+// and reads and for the lane deal (levels.hip), and with it the tail rule that thins the
+// rows' padding to keep a run's last bundle in one pass.
 //
 // Plain C++: no std::, no braced-list loops, so the same text compiles as host code
 // (g++) and as __host__ __device__ code (hipcc).
@@ -62,6 +65,35 @@ FA_SLAB_FN int64_t slab_row_bytes(int sw) { return (int64_t)(sw + 2) * 8; }
 FA_SLAB_FN int64_t slab_map_lds(int64_t F1) {
   return F1 <= kSlabMapMaxF1 ? ((F1 * 2 + 15) & ~(int64_t)15) : 0;
 }
+
+// ---- row layout, defined once -----------------------------------------------------------
+// A row holds sw * 8 data bytes; one 16-B pad slot follows every 2^s rows (pad shift s,
+// 0 .. kSlabPadMax).  s = 0 is the layout above: every row padded, stride (sw + 2) * 8, an
+// odd number of 16-B slots, so rows start on all 16 slot columns of the 256-B bank row.
+// s > 0 thins the padding: at sw = 16 row u starts on column (8u + (u >> s)) mod 16, which
+// still reaches every column, for 16 / 2^s bytes of padding per row instead of 16.
+// Every builder and reader of a slab (count.hip), the lane deal (levels.hip
+// k_dl_lane_assign) and the CPU bank model (benchmarks/lds_bank_model.py, through the
+// fa_slab_row_* exports) take a row's place from these two functions.
+constexpr int kSlabPadMax = 3;
+
+// byte offset of row u
+FA_SLAB_FN int64_t slab_row_off(int sw, int s, int64_t u) { return u * sw * 8 + (u >> s) * 16; }
+// 16-B slot column (0 .. 15) of row u's first slot in the 256-B bank row: (slab_row_off >> 4)
+// mod 16 for the even widths the kernels have, in 32-bit arithmetic (the lane deal asks per
+// record and read position)
+FA_SLAB_FN int slab_row_col(int sw, int s, int u) {
+  return (int)(((uint32_t)u * (uint32_t)(sw >> 1) + ((uint32_t)u >> s)) & 15u);
+}
+// bytes of n rows (the accumulators start here)
+FA_SLAB_FN int64_t slab_rows_bytes(int sw, int s, int64_t n) {
+  return n * sw * 8 + ((n + ((int64_t)1 << s) - 1) >> s) * 16;
+}
+// A layout in one int, for the arguments that used to carry the width alone (the count's
+// launcher, the device plan's lane deal, fa_slab_workgroups): pad shift 0 is the bare width.
+FA_SLAB_FN int slab_layout(int sw, int s) { return sw | (s << 8); }
+FA_SLAB_FN int slab_layout_sw(int layout) { return layout & 0xFF; }
+FA_SLAB_FN int slab_layout_pad(int layout) { return (layout >> 8) & 0xFF; }
 
 // Slab width for n_used items and C candidates in lds bytes (accb: LDS bytes per
 // accumulator: 4, 2 or 1): the first width in the measured order whose accumulator
@@ -139,6 +171,45 @@ FA_SLAB_FN int64_t slab_acc_words(int64_t n_acc) { return (n_acc + 3) & ~(int64_
 // Dynamic LDS bytes of one workgroup: slab rows, n_acc_words u32 accumulators, map
 FA_SLAB_FN int64_t slab_kernel_lds(int64_t n_used, int sw, int64_t n_acc_words, int64_t map_bytes) {
   return n_used * slab_row_bytes(sw) + n_acc_words * 4 + map_bytes;
+}
+
+// ... with the rows at pad shift s (s = 0: slab_kernel_lds)
+FA_SLAB_FN int64_t slab_kernel_lds_pack(int64_t n_used, int sw, int s, int64_t n_acc_words, int64_t map_bytes) {
+  return slab_rows_bytes(sw, s, n_used) + n_acc_words * 4 + map_bytes;
+}
+
+// ---- the tail rule (TUNING.dl_tail_bundle) ----------------------------------------------
+// A bundle that holds every remaining level of the run is worth one pass at width 16 even
+// where the rule above would split it: the split costs a second build of every slab.  The
+// packed rule asks for all C candidates in ONE pass of 16-word slabs, with the smallest
+// pad shift that leaves room for them: width 16 and *s, *cap = that capacity.  Where no
+// shift fits, the answer is slab_width's own (*s = 0).
+FA_SLAB_FN int slab_pack_width(int64_t n_used, int64_t C, double lds, double accb, int64_t* cap, int* s) {
+  for (int q = 0; q <= kSlabPadMax; ++q) {
+    const int64_t c = (int64_t)((lds - (double)slab_rows_bytes(16, q, n_used)) / accb);
+    if (c >= C) { *cap = c; *s = q; return 16; }
+  }
+  *s = 0;
+  return slab_width(n_used, C, lds, accb, cap);
+}
+// C candidates fit one packed pass
+FA_SLAB_FN bool slab_pack_fits(int64_t n_used, int64_t C, double lds, double accb) {
+  const int64_t c = (int64_t)((lds - (double)slab_rows_bytes(16, kSlabPadMax, n_used)) / accb);
+  return C >= 1 && c >= C;
+}
+// The levels of a bundle (C[0 .. L) candidates each) that the rule above accepts at accb:
+// level 0 stands (its own one-pass test is the generator's), level l joins while the total
+// with it fits one pass -- the device chain's capacity test (gen.hip k_dl_decide), replayed.
+// The chain's growth and bound tests do not depend on the capacity, so this is where a
+// chain run without the tail rule would have stopped.
+FA_SLAB_FN int slab_tail_cut(const int64_t* C, int L, int64_t n_used, double lds, double accb) {
+  int64_t total = L > 0 ? C[0] : 0;
+  int l = L > 0 ? 1 : 0;
+  for (; l < L; ++l) {
+    if (total + C[l] > slab_cap(n_used, total + C[l], lds, accb)) break;
+    total += C[l];
+  }
+  return l;
 }
 
 // Workgroups of a slab count: one per slab, at most 256 CUs x the workgroups of

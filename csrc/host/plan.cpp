@@ -30,11 +30,26 @@ FA_API int64_t fa_slab_total_limit(int64_t n_used, double lds, double accb) {
 }
 FA_API int64_t fa_slab_map_lds(int64_t F1) { return slab_map_lds(F1); }
 // n_acc accumulator words (round_acc: rounded as the kernel allocates them), map_bytes
-// of rank map, budget: LDS bytes of a CU's share
+// of rank map, budget: LDS bytes of a CU's share; sw: the width, or a slab_layout
 FA_API int64_t fa_slab_workgroups(int64_t nslabs, int64_t n_used, int sw, int64_t n_acc, int round_acc,
                                   int64_t map_bytes, int64_t budget) {
   return slab_workgroups(nslabs, budget,
-                         slab_kernel_lds(n_used, sw, round_acc ? slab_acc_words(n_acc) : n_acc, map_bytes));
+                         slab_kernel_lds_pack(n_used, slab_layout_sw(sw), slab_layout_pad(sw),
+                                              round_acc ? slab_acc_words(n_acc) : n_acc, map_bytes));
+}
+// The row layout (fa_slab.h): byte offset and 16-B slot column of row u, bytes of n rows,
+// the layout code of (sw, s)
+FA_API int64_t fa_slab_row_off(int sw, int s, int64_t u) { return slab_row_off(sw, s, u); }
+FA_API int fa_slab_row_col(int sw, int s, int64_t u) { return slab_row_col(sw, s, (int)u); }
+FA_API int64_t fa_slab_rows_bytes(int sw, int s, int64_t n) { return slab_rows_bytes(sw, s, n); }
+FA_API int fa_slab_layout(int sw, int s) { return slab_layout(sw, s); }
+// The tail rule: one packed pass at width 16 (*s: its pad shift), else slab_width's answer;
+// the levels of C[0 .. L) the unpacked rule accepts
+FA_API int fa_slab_pack_width(int64_t n_used, int64_t C, double lds, double accb, int64_t* cap, int* s) {
+  return slab_pack_width(n_used, C, lds, accb, cap, s);
+}
+FA_API int fa_slab_tail_cut(const int64_t* C, int L, int64_t n_used, double lds, double accb) {
+  return slab_tail_cut(C, L, n_used, lds, accb);
 }
 // The accumulator width of a slab count asked with accb bytes per accumulator (weighted
 // rows: u32): the cls mode bit of fa_hip_count_slab_rec_cls, and in *n_acc the u32 words

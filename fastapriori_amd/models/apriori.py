@@ -407,6 +407,17 @@ class FastApriori:
         # the narrowest accumulators a bundle's count may take where they move its slab up
         # to width 16 (fa_slab.h slab_acc_upgrade); the bundling stays the rule's at accb
         self._dl_cnt_accb = 1.0 if acc8 == 2 else accb
+        # the tail rule (TUNING.dl_tail_bundle): unit weights, the rank map in LDS, enough rows.
+        # It decides which levels share a bundle, and with them the count all-reduces, so every
+        # rank must take the same decision: the rows are the database's lines per counting rank
+        # (all of them when each rank counts the whole database), not this rank's own shard, and
+        # the packed pass's accumulator bytes follow the knobs alone, not the accumulators this
+        # rank's own row count gave its other bundles (acc8 above)
+        counters = 1 if self.cand_par else max(1, self.comm.world_size)
+        tail_rows = int(self.stats["n_lines"]) // counters
+        self._dl_tail_accb = 0.0            # bytes per accumulator of a packed tail bundle; 0: rule off
+        if TUNING.dl_tail_bundle and unit and Pm.slab_map_lds(F1) > 0 and tail_rows >= TUNING.dl_acc8_min_rows:
+            self._dl_tail_accb = 1.0 if int(TUNING.dl_acc8_bundles) else 2.0 if TUNING.dl_acc16_bundles else 4.0
         c_bound = int(lds // accb)
         st = torch.cuda.current_stream(self._dev).cuda_stream
         f2 = self._f2_dev
@@ -439,8 +450,9 @@ class FastApriori:
             b0 = self._bytes_moved()
             with roctx_range(f"dlevel{k}"), tm.phase(f"level{k}"):
                 max_lv = min(K.kDlMaxM - m0 + 1, K.kDlMaxLevels)
-                if self.cfg.max_level:
-                    max_lv = min(max_lv, self.cfg.max_level - k + 1)
+                tail_levels = 0                 # a bundle of this many levels reaches --max-level
+                if self.cfg.max_level and self.cfg.max_level - k + 1 <= max_lv:
+                    max_lv = tail_levels = self.cfg.max_level - k + 1
                 if not TUNING.bundle_levels or k - 1 > TUNING.bundle_max_prefix:
                     max_lv = 1
                 post = TUNING.dl_post and max_lv > 1
@@ -453,7 +465,9 @@ class FastApriori:
                     self._dl_stage(S, pend)
                 with roctx_range("gen"):
                     c = Pm.dl_bundle_gen(S, P0, n_src, n_const, n_bound, m0, F1, c_bound, lds, TUNING.bundle_growth,
-                                         max_lv, st, post=post, accb=accb)
+                                         max_lv, st, post=post, accb=accb,
+                                         tail_accb=self._dl_tail_accb if post else 0.0,
+                                         tail_levels=tail_levels if max_lv > 1 else 0)
                 if c[K.kDlOverBound]:
                     raise RuntimeError(f"device bundle at level {k}: |F_{k - 1}| exceeds its bound {n_bound}")
                 if c[K.kDlEnd]:
@@ -471,11 +485,11 @@ class FastApriori:
                 Cs = S.desc["C"][:L].copy()
                 C = int(Cs.sum())
                 done = int(S.post.done) if post else 0
-                sw = int(S.post.sw) if done else 0
+                sw, pad = Pm.slab_layout_split(int(S.post.sw)) if done else (0, 0)
                 acc_bytes = int(S.post.accb) if done else int(accb)   # (dl_post writes what it took)
                 if multi is not None:
                     cnt = multi[1]
-                    sw = int(Pm.LAST_LEVEL_PLAN.get("sw", 0))
+                    sw, pad = int(Pm.LAST_LEVEL_PLAN.get("sw", 0)), 0
                     acc_bytes = int(self._dl_mp_accb)
                 elif done == 2:
                     # planned and counted by fa_hip_dl_more's post step (no trim due)
@@ -494,7 +508,7 @@ class FastApriori:
                     with tm.phase("count"), roctx_range("count"):
                         v = self._count_view(db)
                         cnt = Pm.dl_count(S, plan, v["roff"], v["ranks"], v["src"], v["ncols"], F1, v["wword"])
-                    sw, acc_bytes = int(plan["sw"]), int(plan.get("accb", 4.0))
+                    sw, pad, acc_bytes = int(plan["sw"]), int(plan.get("pad", 0)), int(plan.get("accb", 4.0))
                 # candidate distribution: the candidates this rank counted (non-zero
                 # before the sum; read back with the results, for the stats)
                 nz = torch.count_nonzero(cnt) if self.cand_par else None
@@ -505,7 +519,7 @@ class FastApriori:
             hbm_rows = (db["ranks"].numel() * db["ranks"].element_size()
                         + db["roff"].numel() * db["roff"].element_size())
             pend.append(dict(k=k, L=L, m0=m0, C=Cs, rows=rows_a, cnt=cnt_a, ro=ro, co=co, hbm_rows=int(hbm_rows),
-                             n_par=S.desc["n"][:L].copy(), sw=sw, acc_bytes=acc_bytes, used=n_used,
+                             n_par=S.desc["n"][:L].copy(), sw=sw, pad=pad, acc_bytes=acc_bytes, used=n_used,
                              T=int(db["roff"].numel() - 1),
                              ms=(time.perf_counter() - t0) * 1e3, bytes=self._bytes_moved() - b0,
                              G=c[K.kDlGl:K.kDlGl + L].copy(), nz=nz))
@@ -527,6 +541,12 @@ class FastApriori:
         # (first level, levels, candidates, used items, slab width, accumulator bytes) per bundle
         self.stats["device_bundle_shapes"] = [(int(p["k"]), int(p["L"]), int(p["C"].sum()), int(p["used"]),
                                                int(p["sw"]), int(p["acc_bytes"])) for p in pend]
+        # ... and the pad shift of each bundle's slab rows (> 0: the tail rule's packed pass)
+        self.stats["device_bundle_pads"] = [int(p["pad"]) for p in pend]
+        for p in pend:                      # one entry per bundle, under its first level
+            self.stats.setdefault("level_info", {})[int(p["k"])] = dict(
+                kernel="slab_dev", bundled=int(p["L"]), C=int(p["C"].sum()), used=int(p["used"]), sw=int(p["sw"]),
+                pad=int(p["pad"]), acc_bytes=int(p["acc_bytes"]))
         self.stats["device_levels"] = int(sum(p["L"] for p in pend))
         return nxt
 
@@ -707,8 +727,11 @@ class FastApriori:
         # prefixes past kDlInline ids ride in gpre (levels.hip); a bundle needing more than
         # this room is planned by dl_plan with the exact size instead
         K = Pm.dl()
-        gpre_n = n_bound * m0 if m0 > K.kDlInline else (c_bound * (m0 + 4) if m0 + K.kDlMaxLevels > K.kDlInline else 0)
-        b = S.post_buffers(F1, c_bound, n_bound + c_bound, min(gpre_n, 1 << 24))
+        # (a packed tail bundle holds up to the budget's bytes / its accumulator bytes)
+        tail_accb = getattr(self, "_dl_tail_accb", 0.0)
+        c_cap = max(c_bound, int(lds // tail_accb)) if tail_accb else c_bound
+        gpre_n = n_bound * m0 if m0 > K.kDlInline else (c_cap * (m0 + 4) if m0 + K.kDlMaxLevels > K.kDlInline else 0)
+        b = S.post_buffers(F1, c_cap, n_bound + c_cap, min(gpre_n, 1 << 24))
         P = S.post
         P.item_map, P.rec, P.part, P.out = (b["item_map"].data_ptr(), b["rec"].data_ptr(), b["part"].data_ptr(),
                                             b["out"].data_ptr())
@@ -868,7 +891,7 @@ class FastApriori:
                 self._level_recs.append((dict(phase="level", k=kk, candidates=int(p["C"][l]), frequent=F,
                                               ms=p["ms"] * share, groups=int(p["G"][l]), bundled_with=p["k"],
                                               bytes_reduced=int(p["bytes"] * share), kernel="slab_rec_dev",
-                                              hbm_bytes_est=hbm, slab_words=p["sw"], acc_bytes=p["acc_bytes"],
+                                              hbm_bytes_est=hbm, slab_words=p["sw"], slab_pad=p["pad"], acc_bytes=p["acc_bytes"],
                                               used_items=p["used"],
                                               rows=p["T"], _share=share),
                                          f"level{p['k']}"))

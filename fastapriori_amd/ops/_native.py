@@ -49,6 +49,13 @@ _HOST_SIGS = {
     "fa_slab_workgroups": (i64, [i64, i64, C.c_int, i64, C.c_int, i64, i64]),
     "fa_slab_acc_mode": (C.c_int, [dbl, C.c_int, i64, I64P]),
     "fa_slab_acc_upgrade": (C.c_int, [i64, i64, dbl, dbl, C.POINTER(C.c_int), I64P, C.POINTER(dbl)]),
+    # ... the row layout (pad shift s) and the tail rule
+    "fa_slab_row_off": (i64, [C.c_int, C.c_int, i64]),
+    "fa_slab_row_col": (C.c_int, [C.c_int, C.c_int, i64]),
+    "fa_slab_rows_bytes": (i64, [C.c_int, C.c_int, i64]),
+    "fa_slab_layout": (C.c_int, [C.c_int, C.c_int]),
+    "fa_slab_pack_width": (C.c_int, [i64, i64, dbl, dbl, I64P, C.POINTER(C.c_int)]),
+    "fa_slab_tail_cut": (C.c_int, [vp, C.c_int, i64, dbl, dbl]),
     "fa_trim_estimate": (None, [vp, i64, dbl, C.c_int, C.POINTER(dbl), C.POINTER(dbl)]),
     # the device bundle loop's slots, limits, mode bits and struct layouts by name (csrc/host/fa_dl.h)
     "fa_dl_layout": (cp, [C.c_int, I64P]),
@@ -110,6 +117,7 @@ _HIP_SIGS = {
     "fa_hip_dl_more": (C.c_int, [C.c_int, vp, i64, i64, vp, vp, dbl, C.c_int, dbl, dbl, i64, vp, vp, vp, vp]),
     "fa_hip_dl_plan": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, i64, vp, i64, vp, i64, C.c_int, vp]),
     "fa_hip_set_lane_deal": (None, [C.c_int]),
+    "fa_hip_set_dl_tail": (None, [dbl, C.c_int]),
     "fa_hip_set_piece_part": (C.c_int, [C.c_int, C.c_int]),
     "fa_hip_dl_gpre_need": (i64, [vp, C.c_int]),
     "fa_hip_dl_plan_window": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, i64, vp, i64, vp, i64, i64, i64, C.c_int,

@@ -839,6 +839,71 @@ def slab_total_limit(n_used: int, lds: int, accb: int = 4) -> int:
     return int(_native.host().fa_slab_total_limit(int(n_used), float(lds), float(accb)))
 
 
+def slab_layout(sw: int, pad: int = 0) -> int:
+    """A slab's width and pad shift in one int (fa_slab.h slab_layout; pad 0: the bare width):
+    what the count's launcher, the device plan and _slab_workgroups take as `sw`."""
+    return int(_native.host().fa_slab_layout(int(sw), int(pad)))
+
+
+def slab_layout_split(layout: int) -> tuple[int, int]:
+    """(width, pad shift) of a slab_layout."""
+    return int(layout) & 0xFF, (int(layout) >> 8) & 0xFF
+
+
+def slab_row_off(sw: int, pad: int, u: int) -> int:
+    """LDS byte offset of slab row u at pad shift `pad` (fa_slab.h slab_row_off)."""
+    return int(_native.host().fa_slab_row_off(int(sw), int(pad), int(u)))
+
+
+def slab_row_col(sw: int, pad: int, u: int) -> int:
+    """16-B slot column (0 .. 15) of slab row u in the 256-B bank row (fa_slab.h slab_row_col)."""
+    return int(_native.host().fa_slab_row_col(int(sw), int(pad), int(u)))
+
+
+def slab_rows_bytes(sw: int, pad: int, n: int) -> int:
+    """LDS bytes of n slab rows at pad shift `pad`: the accumulators start there."""
+    return int(_native.host().fa_slab_rows_bytes(int(sw), int(pad), int(n)))
+
+
+def slab_pack_width(n_used: int, C: int, lds: int, accb: float = 1) -> tuple[int, int, int]:
+    """The tail rule's (SW, capacity, pad shift): all C candidates in one pass of 16-word
+    slabs at the smallest pad shift that leaves them room, else slab_width's answer at pad
+    shift 0 (fa_slab.h slab_pack_width)."""
+    cap, pad = ctypes.c_int64(0), ctypes.c_int(0)
+    sw = _native.host().fa_slab_pack_width(int(n_used), int(C), float(lds), float(accb), ctypes.byref(cap),
+                                           ctypes.byref(pad))
+    return int(sw), int(cap.value), int(pad.value)
+
+
+def slab_tail_cut(Cs, n_used: int, lds: int, accb: float = 4) -> int:
+    """The levels of a bundle with Cs[l] candidates per level that the unpacked rule accepts
+    (fa_slab.h slab_tail_cut: the device chain's capacity test, replayed)."""
+    c = np.ascontiguousarray(Cs, dtype=np.int64)
+    return int(_native.host().fa_slab_tail_cut(c.ctypes.data, int(c.size), int(n_used), float(lds), float(accb)))
+
+
+def dl_tail_plan(Cs, n_used: int, lds: int, accb: float, cnt_accb: float, ends: bool) -> tuple[int, int, int, int]:
+    """Test hook (no caller in the package: FastApriori reads the decision back from the post
+    step).  Host mirror of the post step's tail rule (gen.hip dl_tail) for a chain that accepted
+    Cs[l] candidates per level: (levels kept, SW, pad shift, capacity).  The bundle stays
+    whole in one packed pass where the unpacked rule would split it, it ends the run
+    (`ends`) and it fits; else it is the unpacked rule's bundle."""
+    Cs = [int(c) for c in Cs]
+    Lp = slab_tail_cut(Cs, n_used, lds, accb)
+    if Lp < len(Cs) and ends:
+        sw, cap, pad = slab_pack_width(n_used, sum(Cs), lds, cnt_accb)
+        if sw == 16 and sum(Cs) <= cap:
+            return len(Cs), sw, pad, cap
+    C = sum(Cs[:Lp])
+    sw, cap = slab_width(n_used, C, lds, accb)
+    if cnt_accb < accb:
+        sw_c, cap_c, accb_c = ctypes.c_int(sw), ctypes.c_int64(cap), ctypes.c_double(accb)
+        _native.host().fa_slab_acc_upgrade(int(n_used), int(C), float(lds), float(cnt_accb), ctypes.byref(sw_c),
+                                           ctypes.byref(cap_c), ctypes.byref(accb_c))
+        sw, cap = int(sw_c.value), int(cap_c.value)
+    return Lp, sw, 0, cap
+
+
 def slab_map_lds(F1: int) -> int:
     """LDS bytes of k_count_slab_rec's u16 rank -> slab-row map (0: it stays in global memory)."""
     return int(_native.host().fa_slab_map_lds(int(F1)))
@@ -884,12 +949,13 @@ def _slab_count(*, roff, ranks, src, ncols: int, item_map, F1: int, n_used: int,
     single-writer byte accumulators (fa_slab.h slab_acc_mode; weighted rows count into u32);
     cls: kSlabCls when rec carries class-layout flags; sup_frac: _slab_dense.
     round_acc, map_bytes: what the caller charges a workgroup's LDS (_slab_workgroups;
-    csrc/host/fa_slab.h lists the callers' charges)."""
+    csrc/host/fa_slab.h lists the callers' charges).  sw: the width, or a slab_layout."""
     K = dl()
-    nslabs = ((ncols + 63) // 64 + sw - 1) // sw
+    width = slab_layout_split(sw)[0]
+    nslabs = ((ncols + 63) // 64 + width - 1) // width
     acc_mode, nacc = _slab_acc_mode(accb, wword is not None, C)
     n_wg = _slab_workgroups(nslabs, n_used, sw, nacc, round_acc, map_bytes)
-    mode = cls | (K.kSlabDense if _slab_dense(wword, sw, sup_frac) else 0) | acc_mode
+    mode = cls | (K.kSlabDense if _slab_dense(wword, width, sup_frac) else 0) | acc_mode
     _hip_call("fa_hip_count_slab_rec_cls", roff, ranks, src, ncols, item_map, F1, n_used, gpre, rec, G, C, wword,
               out, sw, n_wg, bm, bm_ld, st, bm_rows, g_dev, mode)
 
@@ -1800,12 +1866,15 @@ def dl_lds_budget(F1: int) -> int:
 
 def dl_bundle_gen(S: DeviceLevelState, P0: int, n_src: int | None, n_const: int, n_bound: int, m0: int, F1: int,
                   c_bound: int, lds: int, growth: float, max_levels: int, stream: int, post: bool = False,
-                  accb: float = 4.0) -> np.ndarray:
+                  accb: float = 4.0, tail_accb: float = 0.0, tail_levels: int = 0) -> np.ndarray:
     """Candidates of a device bundle: level 0 from F_{k-1} rows P0 and the speculative
     levels 1 .. max_levels-1 (accepted on the device), all queued before ONE
     synchronisation (accb: LDS bytes per slab accumulator, 2 = packed u16 counters).
     Returns the control block (host int64 [kDlCtl]); S.desc[:L] describes the accepted
-    levels (L = ctl[kDlLevels])."""
+    levels (L = ctl[kDlLevels]).  tail_accb > 0 (with post): the tail rule
+    (TUNING.dl_tail_bundle, gen.hip dl_tail) -- a bundle that ends the run stays whole in one
+    packed pass at width 16 with tail_accb bytes per accumulator; tail_levels > 0: a bundle of
+    that many levels reaches --max-level.  Both decide the bundling: every rank passes the same."""
     lib, K = _native.hip(), dl()
     info = np.zeros(2, dtype=np.int64)
     for _ in range(6):
@@ -1825,6 +1894,7 @@ def dl_bundle_gen(S: DeviceLevelState, P0: int, n_src: int | None, n_const: int,
             return c.copy()
         S.post.done = 0
         lane_deal(lib, S.rows_hint)    # (the post step's plan)
+        lib.fa_hip_set_dl_tail(float(tail_accb) if post else 0.0, int(tail_levels))
         rc = lib.fa_hip_dl_more(F1, _p(S.ws), S.ws.numel(), int(S.info[0]), _p(S.ctl), _p(S.ctl_h), float(growth),
                                 int(max_levels), float(lds), float(accb), int(c_bound), S.desc.ctypes.data,
                                 info.ctypes.data,
@@ -1851,13 +1921,17 @@ def lane_deal(lib, rows: int) -> None:
 
 
 def dl_plan(S: DeviceLevelState, L: int, F1: int, n_used: int, C: int, lds: int, dev, accb: float = 4.0,
-            cnt_accb: float | None = None) -> dict:
+            cnt_accb: float | None = None, pad: int = 0) -> dict:
     """Device piece plan of a bundle's C candidates (levels.hip fa_hip_dl_plan), queued
     on the stream right after the generator's synchronisation: it depends on the
     candidates only, not on the row layout, so the host's trimming decision runs
     while it executes.  accb: the bytes per accumulator the bundle was accepted with;
     cnt_accb (smaller): taken instead where it moves the slab up to width 16, as the post
-    step does (fa_slab.h slab_acc_upgrade).  Returns the plan for dl_count."""
+    step does (fa_slab.h slab_acc_upgrade).  pad (a test hook: the post step's tail rule picks
+    its own): the slab rows' pad shift, which the lane deal's slot columns and dl_count's launch
+    follow.  The width and capacity are the rule's at pad shift 0; a thinner padding only
+    shrinks the rows' footprint (slab_rows_bytes falls with pad), so what fits there fits here.
+    Returns the plan for dl_count."""
     st = torch.cuda.current_stream(dev).cuda_stream
     sw, cap = slab_width(n_used, C, lds, accb)
     if sw == 0 or C > cap:
@@ -1876,9 +1950,11 @@ def dl_plan(S: DeviceLevelState, L: int, F1: int, n_used: int, C: int, lds: int,
     gpre = torch.empty(max(gn, 1), dtype=_I32, device=dev)
     lane_deal(lib, S.rows_hint)
     _native.check(lib.fa_hip_dl_plan(S.desc.ctypes.data, L, _p(S.ctl), F1, _p(item_map), _p(rec), C,
-                                     _p(part), part.numel(), _p(gpre), gpre.numel(), sw, st), "fa_hip_dl_plan")
+                                     _p(part), part.numel(), _p(gpre), gpre.numel(), slab_layout(sw, pad), st),
+                  "fa_hip_dl_plan")
     out = torch.zeros(C, dtype=_I32, device=dev)
-    return dict(sw=sw, cap=cap, item_map=item_map, rec=rec, out=out, n_used=n_used, C=C, gpre=gpre, accb=accb)
+    return dict(sw=sw, pad=pad, cap=cap, item_map=item_map, rec=rec, out=out, n_used=n_used, C=C, gpre=gpre,
+                accb=accb)
 
 
 def dl_count_multipass(S: DeviceLevelState, F1: int, n_used: int, C: int, lds: int, roff, ranks, src, ncols: int,
@@ -2051,7 +2127,8 @@ def dl_plan_from_post(S: DeviceLevelState, n_used: int) -> dict:
     P, b = S.post, S.post_bufs
     C = int(P.C)
     out = b["out"][:C]
-    return dict(sw=int(P.sw), cap=int(P.cap), item_map=b["item_map"], rec=b["rec"], out=out, n_used=n_used, C=C,
+    sw, pad = slab_layout_split(int(P.sw))          # (the post step reports the layout it took)
+    return dict(sw=sw, pad=pad, cap=int(P.cap), item_map=b["item_map"], rec=b["rec"], out=out, n_used=n_used, C=C,
                 gpre=b["gpre"], accb=float(P.accb))
 
 
@@ -2063,11 +2140,11 @@ def dl_count(S: DeviceLevelState, plan: dict, roff, ranks, src, ncols: int, F1: 
     item_map, rec, out = plan["item_map"], plan["rec"], plan["out"]
     _slab_count(roff=_p(roff), ranks=_p(ranks), src=_p(src), ncols=ncols, item_map=_p(item_map), F1=F1,
                 n_used=n_used, gpre=_p(plan.get("gpre")), rec=_p(rec), g_dev=_p(S.ctl) + 8 * dl().kDlPiecesI32, C=C,
-                wword=_p(wword), out=_p(out), sw=sw, st=st, round_acc=True, map_bytes=slab_map_lds(F1),
-                accb=plan.get("accb", 4.0))
+                wword=_p(wword), out=_p(out), sw=slab_layout(sw, plan.get("pad", 0)), st=st, round_acc=True,
+                map_bytes=slab_map_lds(F1), accb=plan.get("accb", 4.0))
     LAST_LEVEL_PLAN.clear()
     LAST_LEVEL_PLAN.update(kernel="slab_dev", rows=int(roff.numel() - 1), used=n_used, sw=sw, cap=cap, passes=1,
-                           pieces=-1, slab_reads=0, m=-1, C=C)
+                           pieces=-1, slab_reads=0, m=-1, C=C, pad=int(plan.get("pad", 0)))
     # (item_map and rec may be freed now: the caching allocator hands their blocks only
     # to work queued later on this stream)
     return out

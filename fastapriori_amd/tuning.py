@@ -63,6 +63,17 @@ class Tuning:
     # 6.03 ms) and above, no measurable difference at 100K rows (1.08-1.19 ms either way),
     # where the bundles stay on the accumulators the rule gave them
     dl_acc8_min_rows: int = 1 << 20
+    # the tail rule (csrc/host/fa_slab.h, gen.hip dl_tail): a device bundle that holds every
+    # remaining level of the run -- the chain ran out of candidates, or --max-level ends the
+    # mining inside it -- is counted in ONE pass of 16-word slabs whose rows are padded one
+    # in 2, 4 or 8 instead of each (the pad shift; the smallest that leaves the accumulators
+    # room), where the slab rule would split it and build every slab twice.  Unit weights, the
+    # rank map in LDS, bundles planned by the post step (dl_post), and at least
+    # dl_acc8_min_rows lines per counting rank (the database's lines / ranks, or all of them
+    # when every rank counts the whole database): the rule decides which levels share a
+    # bundle and its all-reduce, so it never looks at a rank's own shard.  Every other bundle
+    # is cut exactly as without the knob.
+    dl_tail_bundle: bool = True
     mp_window_items: bool = True        # window-by-window levels: each window's slab holds only its own used items
     # window-by-window levels: a window counts only the rows holding >= k of its own items
     # (its items' bitmap compacted to them, count.hip k_win_compact) when the binomial
