@@ -906,9 +906,11 @@ constexpr int kM4Ld = kMT4 * kMW / 256;   // staged words per thread and operand
 // bit becomes the e2m1 nibble 0b0001 (0.5; both block scales 2^1 make each product 1).
 // The transactions may sit in any k order that A and B share, so element (dword d,
 // nibble n) of a lane takes transaction 4n + d of its 32: dword d is (x >> d) &
-// 0x11111111, two VALU ops, where bits -> i8 bytes cost ~3 per 4 bits.  The f32 sums
-// are exact integers while a workgroup's chunk holds <= 2^24 transactions
-// (fa_hip_pair_gram_mfma caps kchunk).
+// 0x11111111, two VALU ops, where bits -> i8 bytes cost ~3 per 4 bits.  Every f32
+// partial sum is an exact integer while a workgroup's chunk holds <= 2^24 transactions
+// (fa_hip_pair_gram_mfma caps kchunk at 2^18 words), and the epilogue converts it with a
+// plain cast: adding 0.5 first would be a tie in [2^23, 2^24), where f32 spacing is 1,
+// and round every odd count up to the even one above it.
 typedef int fa_v8i __attribute__((ext_vector_type(8)));
 typedef float fa_v16f __attribute__((ext_vector_type(16)));
 constexpr int kFp4Scale = 128;   // E8M0 2^1
@@ -1020,7 +1022,7 @@ __global__ __launch_bounds__(256) void k_pair_gram_mfma4(BmView bm, int32_t F1,
       for (int g = 0; g < 16; ++g) {
         const int row = ti * kMT4 + wr + 32 * i + (g & 3) + 8 * (g >> 2) + 4 * h;
         const int col = tj * kMT4 + wc + 32 * j + r;
-        const uint32_t v = kFp4 ? (uint32_t)(acc[i][j][g] + 0.5f) : (uint32_t)acc[i][j][g];
+        const uint32_t v = (uint32_t)acc[i][j][g];   // kFp4: an exact integer (<= 2^24), converted as it is
         if (row < col && col < F1 && v) atomicAdd(&out[(int64_t)row * F1 + col], v * scale);
       }
 }
@@ -1176,7 +1178,7 @@ __global__ __launch_bounds__(256) void k_pair_gram_fp4(BmView bm, int32_t F1,
       for (int g = 0; g < 16; ++g) {
         const int row = ti * kMT4 + wr + 32 * i + (g & 3) + 8 * (g >> 2) + 4 * h;
         const int col = tj * kMT4 + wc + 32 * j + r;
-        const uint32_t v = (uint32_t)(acc[i][j][g] + 0.5f);
+        const uint32_t v = (uint32_t)acc[i][j][g];   // an exact integer (<= 2^24): converted as it is
         if (row < col && col < F1 && v) atomicAdd(&out[(int64_t)row * F1 + col], v * scale);
       }
 }
@@ -1822,7 +1824,9 @@ FA_API int fa_hip_pair_gram_mfma(const uint64_t* bm, int32_t F1, int64_t rs, int
   int64_t kchunk = (W + nk - 1) / nk;
   kchunk = std::max<int64_t>(kMW, (kchunk + kMW - 1) / kMW * kMW);
   // fp4: the FP4 form (T40I10D100M pair phase 68 -> 46 ms); 0: the i8 form (a test oracle)
-  if (fp4) kchunk = std::min<int64_t>(kchunk, (int64_t)1 << 18);   // f32-exact sums: <= 2^24 transactions
+  // a chunk of <= 2^18 words is <= 2^24 transactions: every f32 sum of the FP4 kernels is
+  // an exact integer <= 2^24 and their cast to uint32 is exact (tests/test_gram_edges.py)
+  if (fp4) kchunk = std::min<int64_t>(kchunk, (int64_t)1 << 18);
   nk = (W + kchunk - 1) / kchunk;
   if (fp4)
     hipLaunchKernelGGL(k_pair_gram_fp4, dim3((unsigned)(nk * ntp)), dim3(256), 0, st, v, F1, W, nt,

@@ -673,14 +673,15 @@ def _bm_view(bm: torch.Tensor, w0: int):
 
 
 def pair_counts_gram(bm: torch.Tensor, W: int, wword, wcls=None, force_popc: bool = False,
-                     fp4: bool = True, raw: bool = False, w0: int = 0) -> torch.Tensor:
+                     fp4: bool = True, raw: bool = False, w0: int = 0, target_wgs: int = 4096) -> torch.Tensor:
     """Pair supports from the item-major bitmaps over words [w0, w0 + W) -> int64
     [F1, F1] (upper triangle).  bm: row-major [F1, Wp] or (device) the 8-word block
     layout [Wp / 8, F1, 8] (build_bitmaps(blocked=True)); wword / wcls cover the W
     words from w0.  Device: the FP4 matrix-core Gram (k_pair_gram_fp4) per weight
     class, scaled by the class weight (FastApriori.scala:233-235's weighted sum), short
     classes by the popcount Gram with per-word weights.  fp4=False: the i8 matrix-core
-    form (kept as a test oracle of the FP4 one)."""
+    form (kept as a test oracle of the FP4 one).  target_wgs: the workgroups a launch
+    aims at; the launchers split the words into that many chunks over the item tiles."""
     F1 = bm.shape[1] if bm.dim() == 3 else bm.shape[0]
     if bm.is_cuda:
         out = torch.zeros((F1, F1), dtype=_I32, device=bm.device)
@@ -690,10 +691,11 @@ def pair_counts_gram(bm: torch.Tensor, W: int, wword, wcls=None, force_popc: boo
             for a, b, wt in segs:
                 _, rs, bs, ptr, woff = _bm_view(bm, w0 + a)
                 if wt > 0:
-                    _hip_call("fa_hip_pair_gram_mfma", ptr, F1, rs, bs, woff, b - a, _p(out), 4096, wt, int(fp4), st)
+                    _hip_call("fa_hip_pair_gram_mfma", ptr, F1, rs, bs, woff, b - a, _p(out), int(target_wgs), wt,
+                              int(fp4), st)
                 else:
                     _hip_call("fa_hip_pair_gram_popc", ptr, F1, rs, bs, woff, b - a,
-                              wword.data_ptr() + 4 * a if wword is not None else None, _p(out), 4096, st)
+                              wword.data_ptr() + 4 * a if wword is not None else None, _p(out), int(target_wgs), st)
         return out if raw else out.to(_I64)
     assert bm.dim() == 2, "the blocked bitmap layout is device-only"
     out = torch.zeros((F1, F1), dtype=_I64)
