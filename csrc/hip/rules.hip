@@ -26,10 +26,14 @@ constexpr int kRuleTPB = 256;
 // One thread per (itemset s, position p) of level k.  Rows of a wave share
 // the same few itemsets, so the binary-search probes of neighbouring lanes
 // mostly hit the same cache lines of level k-1.
+// A subset that is not found (the input is not downward closed, or level k-1 is not
+// sorted) stores sub = -1, conf = 0.0 and raises err to k (atomicMax, as k_sup_mark:
+// the largest such level survives); the caller reads the word before it orders or
+// emits anything, so no -1 is ever used as a row index.
 __global__ __launch_bounds__(kRuleTPB) void k_rule_gen(
     const int32_t* __restrict__ S, int64_t nS, int k, const int32_t* __restrict__ A, int64_t nA,
     const int64_t* __restrict__ cS, const int64_t* __restrict__ cA, int32_t* __restrict__ sub,
-    double* __restrict__ conf) {
+    double* __restrict__ conf, int32_t* __restrict__ err) {
   const int64_t idx = (int64_t)blockIdx.x * kRuleTPB + threadIdx.x;
   if (idx >= nS * k) return;
   const int64_t s = idx / k;
@@ -44,6 +48,7 @@ __global__ __launch_bounds__(kRuleTPB) void k_rule_gen(
   }
   sub[idx] = (int32_t)found;
   conf[idx] = found >= 0 ? (double)cS[s] / (double)cA[found] : 0.0;
+  if (found < 0) atomicMax(err, k);
 }
 
 // Level-wise cut for level k >= 3 (antecedent size k-1 >= 2).  kept_prev /
@@ -89,11 +94,14 @@ inline dim3 rule_grid(int64_t n) { return dim3((unsigned)((n + kRuleTPB - 1) / k
 
 using namespace fa;
 
+// err: one device int32, zero before a build's first level; non-zero after the kernels is
+// the largest level k with a subset missing from level k-1.
 FA_API int fa_hip_rule_gen(const int32_t* S, int64_t nS, int k, const int32_t* A, int64_t nA, const int64_t* cS,
-                           const int64_t* cA, int32_t* sub, double* conf, hipStream_t st) {
+                           const int64_t* cA, int32_t* sub, double* conf, int32_t* err, hipStream_t st) {
   if (nS <= 0 || k < 2) return 0;
   if (nA >= (int64_t)INT32_MAX) return 3;
-  hipLaunchKernelGGL(k_rule_gen, rule_grid(nS * k), dim3(kRuleTPB), 0, st, S, nS, k, A, nA, cS, cA, sub, conf);
+  hipLaunchKernelGGL(k_rule_gen, rule_grid(nS * k), dim3(kRuleTPB), 0, st, S, nS, k, A, nA, cS, cA, sub, conf,
+                     err);
   FA_LAUNCH_RET();
 }
 

@@ -53,12 +53,26 @@ struct RawRule { int64_t ante; int32_t cons; double conf; };
 using namespace fa;
 
 // rows[k-1]: level-k itemsets (sizes[k-1] rows of k ascending ranks, sorted);
-// counts[k-1]: their supports.  levels = K.  tie_pos[r]: position of rank r's
+// counts[k-1]: their supports.  levels_in = K.  tie_pos[r]: position of rank r's
 // token in the consequent tiebreak order.
+// The levels end at the first empty one: nothing is built, and no stats entry written,
+// for it or for a level after it.  A level with rows above an empty one, or an itemset
+// with a subset missing from the level below (the input is not downward closed or not
+// sorted), is an error: *n_rules = -k for the largest such level k, the RuleSet is empty,
+// and no antecedent index of -1 reaches the cut or the sort.
 FA_API RuleSet* fa_rules_build(const int32_t* const* rows, const int64_t* const* counts,
-                               const int64_t* sizes, int levels, const int64_t* tie_pos,
+                               const int64_t* sizes, int levels_in, const int64_t* tie_pos,
                                int nthreads, int64_t* n_rules) {
   auto* rs = new RuleSet();
+  int levels = 0, gap = 0;
+  while (levels < levels_in && sizes[levels] > 0) ++levels;
+  for (int k = 2; k <= levels_in; ++k)
+    if (sizes[k - 1] > 0 && sizes[k - 2] == 0) gap = k;
+  if (gap) {
+    *n_rules = -(int64_t)gap;
+    return rs;
+  }
+  std::atomic<int> bad{0};
   // raw[L] = rules with antecedent size L (L = 1..levels-1), stored at raw[L-1]
   std::vector<std::vector<RawRule>> raw(std::max(0, levels - 1));
   for (int k = 2; k <= levels; ++k) {
@@ -77,11 +91,19 @@ FA_API RuleSet* fa_rules_build(const int32_t* const* rows, const int64_t* const*
           for (int q = 0; q < k; ++q) if (q != p) key[w++] = row[q];
           int64_t a = find_row(A, nA, k - 1, key.data());
           // a >= 0 always holds for a complete miner (anti-monotonicity)
+          if (a < 0) {
+            int cur = bad.load(std::memory_order_relaxed);
+            while (cur < k && !bad.compare_exchange_weak(cur, k, std::memory_order_relaxed)) {}
+          }
           double c = a >= 0 ? (double)counts[k - 1][s] / (double)counts[k - 2][a] : 0.0;
           out[(size_t)(s * k + p)] = RawRule{a, row[p], c};
         }
       }
     });
+  }
+  if (bad.load()) {
+    *n_rules = -(int64_t)bad.load();
+    return rs;
   }
   // level-wise cut
   std::vector<std::vector<char>> keep(raw.size());

@@ -314,6 +314,54 @@ static void test_kernels_and_rules(int nt) {
   }
 }
 
+// fa_rules_build on inputs a complete miner never produces (a saved result can be cut
+// or filtered): an itemset whose subset is missing, a level with rows above an empty
+// one, and trailing empty levels.  The first two are errors and must not index a level
+// with -1 (the sanitizers watch); the last ends the levels early.
+static void test_rules_edges(int nt) {
+  const int64_t tie[3] = {2, 0, 1};
+  auto build = [&](const int32_t* const* rows, const int64_t* const* cnts, const int64_t* sizes, int K,
+                   int64_t* nstats) {
+    int64_t n = 0;
+    void* rs = fa_rules_build(rows, cnts, sizes, K, tie, nt, &n);
+    *nstats = fa_rules_nstats(rs);
+    if (n < 0) CHECK(fa_rules_nante(rs) == 0 && *nstats == 0);
+    fa_rules_free(rs);
+    return n;
+  };
+  const int32_t l1[] = {0, 1, 2}, l2[] = {0, 1, 0, 2}, l3[] = {0, 1, 2};
+  const int64_t c1[] = {5, 4, 3}, c2[] = {3, 2}, c3[] = {2};
+  int64_t ns = -1;
+  {  // {0, 2} without {2} in level 1
+    const int32_t* rows[2] = {l1, l2};
+    const int64_t* cnts[2] = {c1, c2};
+    const int64_t sizes[2] = {2, 2};
+    CHECK(build(rows, cnts, sizes, 2, &ns) == -2);
+  }
+  {  // {0, 1, 2} without {1, 2} in level 2
+    const int32_t* rows[3] = {l1, l2, l3};
+    const int64_t* cnts[3] = {c1, c2, c3};
+    const int64_t sizes[3] = {3, 2, 1};
+    CHECK(build(rows, cnts, sizes, 3, &ns) == -3);
+  }
+  {  // a gap: level 3 above an empty level 2, and level 2 above an empty level 1
+    const int32_t* rows[3] = {l1, l2, l3};
+    const int64_t* cnts[3] = {c1, c2, c3};
+    const int64_t gap2[3] = {3, 0, 1}, gap1[3] = {0, 2, 0};
+    CHECK(build(rows, cnts, gap2, 3, &ns) == -3);
+    CHECK(build(rows, cnts, gap1, 3, &ns) == -2);
+  }
+  {  // trailing empty levels: four rules, one stats entry (before, after, microseconds)
+    const int32_t* rows[4] = {l1, l2, l3, l3};
+    const int64_t* cnts[4] = {c1, c2, c3, c3};
+    const int64_t sizes[4] = {3, 2, 0, 0}, none[4] = {3, 0, 0, 0};
+    CHECK(build(rows, cnts, sizes, 4, &ns) == 4 && ns == 3);
+    CHECK(build(rows, cnts, sizes, 2, &ns) == 4 && ns == 3);
+    CHECK(build(rows, cnts, none, 4, &ns) == 0 && ns == 0);
+    CHECK(build(rows, cnts, none, 0, &ns) == 0 && ns == 0);
+  }
+}
+
 // The slab rule (fa_slab.h) at hand-computed points; tests/test_slab_rule.py sweeps it.
 static void test_slab_rule() {
   const double lds = 163328;
@@ -354,6 +402,7 @@ int main(int argc, char** argv) {
   test_generators(nt);
   test_apriori_gen(nt);
   test_kernels_and_rules(nt);
+  test_rules_edges(nt);
   if (g_fail) {
     std::fprintf(stderr, "%d check(s) failed\n", g_fail);
     return 1;

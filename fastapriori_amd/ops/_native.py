@@ -157,7 +157,7 @@ _HIP_SIGS = {
     "fa_hip_slot_remap": (C.c_int, [vp, i64, vp, vp]),
     "fa_hip_dict_verify": (C.c_int, [vp, vp, i64, vp, vp, vp, vp, i64, vp]),
     "fa_hip_compact_lines": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp]),
-    "fa_hip_rule_gen": (C.c_int, [vp, i64, C.c_int, vp, i64, vp, vp, vp, vp, vp]),
+    "fa_hip_rule_gen": (C.c_int, [vp, i64, C.c_int, vp, i64, vp, vp, vp, vp, vp, vp]),
     "fa_hip_rule_cut": (C.c_int, [vp, vp, i64, C.c_int, vp, vp, vp, vp]),
     "fa_hip_rule_emit": (C.c_int, [vp, vp, vp, vp, vp, i64, vp, vp]),
     "fa_hip_sup_mark": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]),

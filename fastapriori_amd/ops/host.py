@@ -48,7 +48,23 @@ class RuleTable:
         return self.ante[self.ante_off[i]:self.ante_off[i + 1]]
 
 
+def rules_not_closed(bad: int) -> RuntimeError:
+    """The error of both rule builders (this one and ops.primitives.rules_build_device) for a
+    result whose level ``bad`` has an itemset with a subset missing from the level below."""
+    return RuntimeError(f"rules: an itemset of size {bad} has a subset that is not in level {bad - 1} "
+                        "(the levels are not downward closed, or a level is not sorted)")
+
+
+def rules_gap_level(sizes) -> int:
+    """The largest level with rows above an empty level (its subsets are missing), else 0."""
+    return max((k for k in range(2, len(sizes) + 1) if sizes[k - 1] > 0 and sizes[k - 2] == 0), default=0)
+
+
 def rules_build(levels: list[np.ndarray], counts: list[np.ndarray], tie_pos: np.ndarray) -> RuleTable:
+    """Association rules on the CPU (csrc/host/rules.cpp), levels / counts as
+    ops.primitives.rules_build_device.  The levels end at the first empty one (level_stats
+    has no entry for it); a result that is not downward closed or not sorted (a level with
+    rows above an empty one included) raises RuntimeError naming the level."""
     K = len(levels)
     lv = [np.ascontiguousarray(l, dtype=np.int32) for l in levels]
     ct = [np.ascontiguousarray(c, dtype=np.int64) for c in counts]
@@ -63,6 +79,9 @@ def rules_build(levels: list[np.ndarray], counts: list[np.ndarray], tie_pos: np.
     h = lib.fa_rules_build(C.cast(rows_p, C.c_void_p), C.cast(cnt_p, C.c_void_p), sizes.ctypes.data, K,
                            tie.ctypes.data, num_threads(), nr.ctypes.data)
     R = int(nr[0])
+    if R < 0:
+        lib.fa_rules_free(h)
+        raise rules_not_closed(-R)
     na = int(lib.fa_rules_nante(h))
     ns = int(lib.fa_rules_nstats(h))
     ante_off = np.zeros(R + 1, dtype=np.int64)

@@ -25,6 +25,7 @@ import torch
 from ..tuning import TUNING
 from ..utils.env import num_threads
 from . import _native
+from .host import rules_gap_level, rules_not_closed
 
 _I32, _I64 = torch.int32, torch.int64
 PAIR_CHUNK_ROWS = 1 << 18   # rows per pair-kernel chunk (working set ~10 MB: L2 / Infinity Cache resident)
@@ -1368,8 +1369,17 @@ def rules_build_device(levels: list, counts: list, tie_pos: np.ndarray, dev) -> 
     supports.  Returns device tensors ante_off int64 [R+1], ante int32, cons int32 [R],
     conf float64 [R] in recommendation order, plus level_stats [(antecedent size,
     before cut, after cut)] — the same table as the host builder (ops.host.rules_build).
+
+    The levels end at the first empty one (no level_stats entry for it).  A result that is
+    not downward closed or not sorted raises RuntimeError naming the level, as the host
+    builder does: a level with rows above an empty one before any launch, a subset that
+    k_rule_gen does not find through the error word, which is zeroed once, raised by the
+    kernels and read once after the level loop, before anything is ordered or emitted.
     """
     K = len(levels)
+    bad = rules_gap_level([len(l) for l in levels])
+    if bad:
+        raise rules_not_closed(bad)
     empty = dict(ante_off=torch.zeros(1, dtype=_I64, device=dev), ante=torch.zeros(0, dtype=_I32, device=dev),
                  cons=torch.zeros(0, dtype=_I32, device=dev), conf=torch.zeros(0, dtype=torch.float64, device=dev),
                  level_stats=[], level_ms=[])
@@ -1392,6 +1402,7 @@ def rules_build_device(levels: list, counts: list, tie_pos: np.ndarray, dev) -> 
         return cnt_all.data_ptr() + int(cbase[m - 1]) * 8
 
     kept_prev = conf_prev = None
+    err = torch.zeros(1, dtype=_I32, device=dev)
     parts = []          # per level: (flat rule ids kept, conf, sub)
     stats = []
     level_ms = []       # wall ms of each level's generation + cut (the nonzero readback syncs)
@@ -1403,7 +1414,7 @@ def rules_build_device(levels: list, counts: list, tie_pos: np.ndarray, dev) -> 
         sub = torch.empty(nS * k, dtype=_I32, device=dev)
         conf = torch.empty(nS * k, dtype=torch.float64, device=dev)
         _native.check(lib.fa_hip_rule_gen(rows(k), nS, k, rows(k - 1), nA, cnts(k), cnts(k - 1), _p(sub), _p(conf),
-                                          st), "fa_hip_rule_gen")
+                                          _p(err), st), "fa_hip_rule_gen")
         if k == 2:
             kept = torch.ones(nS * k, dtype=torch.uint8, device=dev)
         else:
@@ -1415,6 +1426,9 @@ def rules_build_device(levels: list, counts: list, tie_pos: np.ndarray, dev) -> 
         stats.append((k - 1, nS * k, ids.numel()))
         level_ms.append((time.perf_counter() - t_lv) * 1e3)
         kept_prev, conf_prev = kept, conf
+    bad = int(err.item())
+    if bad:
+        raise rules_not_closed(bad)
     conf_r = torch.cat([c[i] for _, i, c, _ in parts])
     R = conf_r.numel()
     if R == 0:
