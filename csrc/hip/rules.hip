@@ -18,6 +18,7 @@
 //     k_rule_emit then writes the antecedent rows of the sorted rules.
 // Host counterpart (same semantics, CPU runs and tests): csrc/host/rules.cpp.
 #include "fa_hip.h"
+#include "../host/fa_rule_measures.h"
 
 namespace fa {
 
@@ -88,6 +89,154 @@ __global__ __launch_bounds__(kRuleTPB) void k_rule_emit(
   for (int j = 0; j < m; ++j) dst[j] = src[j];
 }
 
+// ---------------------------------------------------------------------------
+// Rule export (all_rules: no counterpart in the reference): EVERY rule A -> c of every
+// frequent S = A + {c}, |S| >= 2, without the cut, selected on confidence (and lift)
+// thresholds and compacted on the device.  Measures: ../host/fa_rule_measures.h.
+//
+// One thread per (S, p) over all levels k = 2..K, addressed as k_sup_mark (condense.hip)
+// does: an int64 index over eoff (K + 2 words, searched in memory), the 32-bit division
+// fast path, rows_all / base / cnt_all / cbase in rules_build_device's layout.
+//   k_rm_count  finds A = S - {S[p]} in level k-1 and c = S[p] in level 1, tests the
+//               thresholds, keeps sub[idx] = A's row (-1: not selected) and leaves the
+//               workgroup's number of selected rules in wgtot (wg_sum);
+//   k_rm_scan   one workgroup: exclusive scan of wgtot into wgoff (wg_scan_chunks), the
+//               total R into ctl[0];
+//   k_rm_emit   writes only the selected rules, at wgoff[workgroup] + the thread's rank
+//               among its workgroup's selected threads (wg_scan_excl): stable in (level,
+//               itemset, position) order and without atomics, so two runs place alike.
+// ctl: two int64 words zeroed by the caller, [0] = R, [1] = the error word (the largest
+// level k with an antecedent missing from level k-1 or a consequent missing from level
+// 1: atomicMax as k_rule_gen); the caller reads both in one copy before it sizes, orders
+// or emits anything.  A pair that raises the error selects nothing.
+// ---------------------------------------------------------------------------
+constexpr int kRmW = kRuleTPB / kWave;
+constexpr int kRmScanTPB = 1024;
+
+struct RmAt {
+  int k, p;
+  int64_t s;
+  const int32_t* row;      // S
+};
+
+__device__ __forceinline__ RmAt rm_locate(const int32_t* __restrict__ rows_all, const int64_t* __restrict__ base,
+                                          const int64_t* __restrict__ eoff, int K, int64_t idx) {
+  // the last k in [2, K] with eoff[k] <= idx (an empty level has eoff[k] == eoff[k+1])
+  int klo = 2, khi = K;
+  while (klo < khi) {
+    const int mid = (klo + khi + 1) >> 1;
+    if (eoff[mid] <= idx) klo = mid; else khi = mid - 1;
+  }
+  RmAt a;
+  a.k = klo;
+  const int64_t local = idx - eoff[klo];
+  // 64-bit division only past 2^32 elements in one level
+  a.s = (local >> 32) == 0 ? (int64_t)((uint32_t)local / (uint32_t)klo) : local / klo;
+  a.p = (int)(local - a.s * klo);
+  a.row = rows_all + base[klo] + a.s * klo;
+  return a;
+}
+
+// row of item c in level 1 (sorted single items), -1 when it is missing
+__device__ __forceinline__ int64_t rm_find1(const int32_t* __restrict__ L1, int64_t n1, int32_t c) {
+  int64_t lo = 0, hi = n1;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    const int32_t x = L1[mid];
+    if (x == c) return mid;
+    if (x < c) lo = mid + 1; else hi = mid;
+  }
+  return -1;
+}
+
+__global__ __launch_bounds__(kRuleTPB) void k_rm_count(
+    const int32_t* __restrict__ rows_all, const int64_t* __restrict__ base, const int64_t* __restrict__ cnt_all,
+    const int64_t* __restrict__ cbase, const int64_t* __restrict__ eoff, int K, int64_t total, RuleSel q,
+    int32_t* __restrict__ sub, int32_t* __restrict__ wgtot, unsigned long long* __restrict__ ctl) {
+  __shared__ int scratch[kRmW];
+  const int64_t idx = (int64_t)blockIdx.x * kRuleTPB + threadIdx.x;
+  int sel = 0;
+  if (idx < total) {
+    const RmAt at = rm_locate(rows_all, base, eoff, K, idx);
+    const int k = at.k;
+    const int64_t rS = cbase[k - 1], rA = cbase[k - 2];       // first rows of level k and of level k-1
+    const int32_t* A = rows_all + base[k - 1];
+    int64_t lo = 0, hi = rS - rA, found = -1;
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      const int c = cmp_skip(A + mid * (k - 1), at.row, k, at.p);
+      if (c == 0) { found = mid; break; }
+      if (c < 0) lo = mid + 1; else hi = mid;
+    }
+    const int64_t c1 = rm_find1(rows_all + base[1], cbase[1], at.row[at.p]);
+    if (found < 0 || c1 < 0) {
+      atomicMax(ctl + 1, (unsigned long long)k);
+    } else {
+      sel = rm_selected(q, cnt_all[rS + at.s], cnt_all[rA + found], cnt_all[c1]) ? 1 : 0;
+    }
+    sub[idx] = sel ? (int32_t)found : -1;
+  }
+  const int tot = wg_sum<kRmW>(sel, scratch);                 // every thread reaches it
+  if (threadIdx.x == 0) wgtot[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(kRmScanTPB) void k_rm_scan(const int32_t* __restrict__ wgtot, int64_t nwg,
+                                                        int64_t* __restrict__ wgoff,
+                                                        unsigned long long* __restrict__ ctl) {
+  __shared__ int scratch[kRmScanTPB / kWave];
+  const int64_t R = wg_scan_chunks<kRmScanTPB / kWave>(
+      nwg, (int64_t)0, scratch, [&](int64_t i) { return (int)wgtot[i]; },
+      [&](int64_t i, int64_t before, int) { wgoff[i] = before; });
+  if (threadIdx.x == 0) ctl[0] = (unsigned long long)R;
+}
+
+// R: the total k_rm_scan left in ctl[0] (the outputs hold R rules; nothing is written past it)
+__global__ __launch_bounds__(kRuleTPB) void k_rm_emit(
+    const int32_t* __restrict__ rows_all, const int64_t* __restrict__ base, const int64_t* __restrict__ cnt_all,
+    const int64_t* __restrict__ cbase, const int64_t* __restrict__ eoff, int K, int64_t total, int64_t N, int sort,
+    const int32_t* __restrict__ sub, const int64_t* __restrict__ wgoff, int64_t R, int64_t* __restrict__ cntS,
+    int64_t* __restrict__ cntA, int64_t* __restrict__ cntC, int32_t* __restrict__ msz, int32_t* __restrict__ aidx,
+    int32_t* __restrict__ cons, double* __restrict__ conf, double* __restrict__ key) {
+  __shared__ int scratch[kRmW];
+  const int64_t idx = (int64_t)blockIdx.x * kRuleTPB + threadIdx.x;
+  const int32_t found = idx < total ? sub[idx] : -1;
+  const int sel = found >= 0 ? 1 : 0;
+  int wg_total;
+  const int before = wg_scan_excl<kRmW>(sel, scratch, wg_total);
+  if (!sel) return;
+  const int64_t o = wgoff[blockIdx.x] + before;
+  if (o >= R) return;
+  const RmAt at = rm_locate(rows_all, base, eoff, K, idx);
+  const int k = at.k;
+  const int32_t c = at.row[at.p];
+  const int64_t c1 = rm_find1(rows_all + base[1], cbase[1], c);   // found by k_rm_count
+  if (c1 < 0) return;
+  const int64_t cS = cnt_all[cbase[k - 1] + at.s], cA = cnt_all[cbase[k - 2] + found], cC = cnt_all[c1];
+  cntS[o] = cS;
+  cntA[o] = cA;
+  cntC[o] = cC;
+  msz[o] = k - 1;
+  aidx[o] = found;
+  cons[o] = c;
+  conf[o] = rm_confidence(cS, cA);
+  key[o] = rm_measure(sort, cS, cA, cC, N);
+}
+
+// the five measures of the kept rules, from their three counts (after the sort and the limit)
+__global__ __launch_bounds__(kRuleTPB) void k_rm_fin(
+    const int64_t* __restrict__ cntS, const int64_t* __restrict__ cntA, const int64_t* __restrict__ cntC, int64_t R,
+    int64_t N, double* __restrict__ support, double* __restrict__ conf, double* __restrict__ lift,
+    double* __restrict__ leverage, double* __restrict__ conviction) {
+  const int64_t i = (int64_t)blockIdx.x * kRuleTPB + threadIdx.x;
+  if (i >= R) return;
+  const int64_t cS = cntS[i], cA = cntA[i], cC = cntC[i];
+  support[i] = rm_support(cS, N);
+  conf[i] = rm_confidence(cS, cA);
+  lift[i] = rm_lift(cS, cA, cC, N);
+  leverage[i] = rm_leverage(cS, cA, cC, N);
+  conviction[i] = rm_conviction(cS, cA, cC, N);
+}
+
 inline dim3 rule_grid(int64_t n) { return dim3((unsigned)((n + kRuleTPB - 1) / kRuleTPB)); }
 
 }  // namespace fa
@@ -119,5 +268,71 @@ FA_API int fa_hip_rule_emit(const int32_t* rows_all, const int64_t* base, const 
   if (R <= 0) return 0;
   hipLaunchKernelGGL(k_rule_emit, rule_grid(R), dim3(kRuleTPB), 0, st, rows_all, base, msz, ante_idx, ante_off,
                      R, ante);
+  FA_LAUNCH_RET();
+}
+
+// The (S, p) elements of levels 2..K and their workgroups, by the launcher's rules (as
+// fa_hip_sup_mark): 0 elements when no level above the first has a row, -3 for a level of
+// >= INT32_MAX rows or a grid that does not fit.  sizes: HOST array of the K row counts.
+static int64_t rm_total(const int64_t* sizes, int K, int64_t* blocks) {
+  int64_t total = 0;
+  for (int k = 1; k <= K; ++k) {
+    if (sizes[k - 1] >= (int64_t)INT32_MAX) return -3;
+    if (k >= 2) total += sizes[k - 1] * k;
+  }
+  *blocks = (total + kRuleTPB - 1) / kRuleTPB;
+  if (*blocks >= (int64_t)INT32_MAX) return -3;
+  return total;
+}
+
+// Selection and count of the exported rules: k_rm_count + k_rm_scan, whatever K.  sizes is a
+// HOST array; every other pointer is device memory: sub int32 [elements], wgtot int32 and
+// wgoff int64 [workgroups of 256 elements], ctl two int64 words that are zero on entry
+// ([0] = R, [1] = error level on return).  0 with no launch when no level above the first
+// has a row; 3 for a level of >= INT32_MAX rows or a grid that does not fit.
+FA_API int fa_hip_rule_measures(const int32_t* rows_all, const int64_t* base, const int64_t* cnt_all,
+                                const int64_t* cbase, const int64_t* eoff, const int64_t* sizes, int K, int64_t N,
+                                double min_conf, int has_lift, double min_lift, int sort, int32_t* sub,
+                                int32_t* wgtot, int64_t* wgoff, int64_t* ctl, hipStream_t st) {
+  int64_t blocks = 0;
+  const int64_t total = rm_total(sizes, K, &blocks);
+  if (total < 0) return 3;
+  if (total == 0) return 0;
+  RuleSel q;
+  q.min_conf = min_conf;
+  q.min_lift = min_lift;
+  q.N = N;
+  q.has_lift = has_lift;
+  q.sort = sort;
+  hipLaunchKernelGGL(k_rm_count, dim3((unsigned)blocks), dim3(kRuleTPB), 0, st, rows_all, base, cnt_all, cbase, eoff,
+                     K, total, q, sub, wgtot, (unsigned long long*)ctl);
+  hipLaunchKernelGGL(k_rm_scan, dim3(1), dim3(kRmScanTPB), 0, st, wgtot, blocks, wgoff, (unsigned long long*)ctl);
+  FA_LAUNCH_RET();
+}
+
+// The R selected rules of fa_hip_rule_measures' sub / wgoff, in (level, itemset, position)
+// order: their three counts, the antecedent's size and row, the consequent, the confidence
+// and the sort measure (each output holds R elements).
+FA_API int fa_hip_rule_measures_emit(const int32_t* rows_all, const int64_t* base, const int64_t* cnt_all,
+                                     const int64_t* cbase, const int64_t* eoff, const int64_t* sizes, int K,
+                                     int64_t N, int sort, const int32_t* sub, const int64_t* wgoff, int64_t R,
+                                     int64_t* cntS, int64_t* cntA, int64_t* cntC, int32_t* msz, int32_t* aidx,
+                                     int32_t* cons, double* conf, double* key, hipStream_t st) {
+  int64_t blocks = 0;
+  const int64_t total = rm_total(sizes, K, &blocks);
+  if (total < 0) return 3;
+  if (total == 0 || R <= 0) return 0;
+  hipLaunchKernelGGL(k_rm_emit, dim3((unsigned)blocks), dim3(kRuleTPB), 0, st, rows_all, base, cnt_all, cbase, eoff,
+                     K, total, N, sort, sub, wgoff, R, cntS, cntA, cntC, msz, aidx, cons, conf, key);
+  FA_LAUNCH_RET();
+}
+
+FA_API int fa_hip_rule_measures_fin(const int64_t* cntS, const int64_t* cntA, const int64_t* cntC, int64_t R,
+                                    int64_t N, double* support, double* conf, double* lift, double* leverage,
+                                    double* conviction, hipStream_t st) {
+  if (R <= 0) return 0;
+  if ((R + kRuleTPB - 1) / kRuleTPB >= (int64_t)INT32_MAX) return 3;
+  hipLaunchKernelGGL(k_rm_fin, rule_grid(R), dim3(kRuleTPB), 0, st, cntS, cntA, cntC, R, N, support, conf, lift,
+                     leverage, conviction);
   FA_LAUNCH_RET();
 }

@@ -18,6 +18,7 @@
 #include <unordered_map>
 
 #include "fa_common.h"
+#include "fa_rule_measures.h"
 
 namespace fa {
 
@@ -256,3 +257,186 @@ FA_API void fa_recommend_topn_cpu(const int64_t* ante_off, const int32_t* ante, 
     }
   });
 }
+
+// ---------------------------------------------------------------------------
+// Rule export (AssociationRules.all_rules; no counterpart in the reference): every rule
+// A -> c of every frequent S = A + {c}, |S| >= 2, WITHOUT the cut, with the measures of
+// fa_rule_measures.h.  Device counterpart (same inputs, selection, order and error):
+// csrc/hip/rules.hip k_rm_count / k_rm_scan / k_rm_emit / k_rm_fin.
+// ---------------------------------------------------------------------------
+namespace fa {
+
+struct RuleMeasureSet {
+  std::vector<int64_t> ante_off, cS, cA, cC;       // R+1, R, R, R
+  std::vector<int32_t> ante, cons;
+  std::vector<double> support, conf, lift, leverage, conviction;
+};
+
+}  // namespace fa
+
+// rows_all / base / cnt_all / cbase: condense.cpp's layout (base[m]: element offset of the
+// size-m level, cbase[m-1]: its first row).  The levels end at the first empty one (the
+// caller rejects rows above an empty level).  Selection: confidence >= min_conf and, with
+// has_lift, lift >= min_lift, in fp64.  Order: the sort measure descending (+inf first),
+// confidence descending, tie_pos[consequent], antecedent size, antecedent row -- a total
+// order; limit >= 0 keeps that many rules.  *n_rules: the rules kept, or -k for the
+// largest level k with an antecedent missing from level k-1 or a consequent missing from
+// level 1 (nothing is built then).  N and every count are at most kRuleCountMax (the
+// caller checks).
+FA_API RuleMeasureSet* fa_rule_measures_cpu(const int32_t* rows_all, const int64_t* base, const int64_t* cnt_all,
+                                            const int64_t* cbase, int K, int64_t N, double min_conf, int has_lift,
+                                            double min_lift, int sort, int64_t limit, const int64_t* tie_pos,
+                                            int nthreads, int64_t* n_rules) {
+  auto* out = new RuleMeasureSet();
+  out->ante_off.push_back(0);
+  *n_rules = 0;
+  int levels = 0;
+  while (levels < K && cbase[levels + 1] > cbase[levels]) ++levels;
+  if (levels < 2) return out;
+  RuleSel q;
+  q.min_conf = min_conf;
+  q.min_lift = min_lift;
+  q.N = N;
+  q.has_lift = has_lift;
+  q.sort = sort;
+  // (S, p) elements in (level, itemset, position) order, in fixed chunks of itemsets:
+  // pass 1 finds and selects (sub: the antecedent's row, -1 when not selected) and counts
+  // per chunk, a scan places the chunks, pass 2 writes the selected rules
+  constexpr int64_t kChunk = 1024;
+  struct Chunk { int k; int64_t s0, s1, e0; };
+  std::vector<Chunk> chunks;
+  int64_t total = 0;
+  for (int k = 2; k <= levels; ++k) {
+    const int64_t nS = cbase[k] - cbase[k - 1];
+    for (int64_t s0 = 0; s0 < nS; s0 += kChunk) {
+      const int64_t s1 = std::min(nS, s0 + kChunk);
+      chunks.push_back(Chunk{k, s0, s1, total + s0 * k});
+    }
+    total += nS * k;
+  }
+  std::vector<int32_t> sub((size_t)total);
+  std::vector<int64_t> coff(chunks.size() + 1, 0);
+  std::atomic<int> bad{0};
+  const int32_t* L1 = rows_all + base[1];
+  const int64_t n1 = cbase[1];
+  parallel_for((int64_t)chunks.size(), nthreads, 1, [&](int64_t b, int64_t e, int) {
+    std::vector<int32_t> key;
+    for (int64_t ci = b; ci < e; ++ci) {
+      const Chunk& c = chunks[(size_t)ci];
+      const int k = c.k;
+      key.resize((size_t)k - 1);
+      const int32_t* S = rows_all + base[k];
+      const int32_t* A = rows_all + base[k - 1];
+      const int64_t rS = cbase[k - 1], rA = cbase[k - 2], nA = rS - rA;
+      int64_t kept = 0;
+      for (int64_t s = c.s0; s < c.s1; ++s) {
+        const int32_t* row = S + s * k;
+        for (int p = 0; p < k; ++p) {
+          int w = 0;
+          for (int j = 0; j < k; ++j) if (j != p) key[w++] = row[j];
+          const int64_t a = find_row(A, nA, k - 1, key.data());
+          const int64_t c1 = find_row(L1, n1, 1, row + p);
+          bool sel = false;
+          if (a < 0 || c1 < 0) {
+            int cur = bad.load(std::memory_order_relaxed);
+            while (cur < k && !bad.compare_exchange_weak(cur, k, std::memory_order_relaxed)) {}
+          } else {
+            sel = rm_selected(q, cnt_all[rS + s], cnt_all[rA + a], cnt_all[c1]);
+          }
+          sub[(size_t)(c.e0 + (s - c.s0) * k + p)] = sel ? (int32_t)a : -1;
+          kept += sel;
+        }
+      }
+      coff[(size_t)ci + 1] = kept;
+    }
+  });
+  if (bad.load()) {
+    *n_rules = -(int64_t)bad.load();
+    return out;
+  }
+  for (size_t i = 0; i < chunks.size(); ++i) coff[i + 1] += coff[i];
+  const int64_t R = coff[chunks.size()];
+  struct Sel { double key, conf; int64_t tie, cS, cA, cC; int32_t msz, aidx, cons; };
+  std::vector<Sel> sel((size_t)R);
+  parallel_for((int64_t)chunks.size(), nthreads, 1, [&](int64_t b, int64_t e, int) {
+    for (int64_t ci = b; ci < e; ++ci) {
+      const Chunk& c = chunks[(size_t)ci];
+      const int k = c.k;
+      const int32_t* S = rows_all + base[k];
+      const int64_t rS = cbase[k - 1], rA = cbase[k - 2];
+      int64_t o = coff[(size_t)ci];
+      for (int64_t s = c.s0; s < c.s1; ++s)
+        for (int p = 0; p < k; ++p) {
+          const int32_t a = sub[(size_t)(c.e0 + (s - c.s0) * k + p)];
+          if (a < 0) continue;
+          const int32_t item = S[s * k + p];
+          const int64_t cS = cnt_all[rS + s], cA = cnt_all[rA + a], cC = cnt_all[find_row(L1, n1, 1, &item)];
+          sel[(size_t)o++] = Sel{rm_measure(sort, cS, cA, cC, N), rm_confidence(cS, cA), tie_pos[item], cS, cA, cC,
+                                 k - 1, a, item};
+        }
+    }
+  });
+  // the order: sorted chunks merged pairwise, as the itemset writer's lines
+  auto less = [](const Sel& x, const Sel& y) {
+    if (x.key != y.key) return x.key > y.key;
+    if (x.conf != y.conf) return x.conf > y.conf;
+    if (x.tie != y.tie) return x.tie < y.tie;
+    if (x.msz != y.msz) return x.msz < y.msz;
+    return x.aidx < y.aidx;
+  };
+  {
+    const int T = (int)std::max<int64_t>(1, std::min<int64_t>(nthreads, R / 4096));
+    std::vector<int64_t> cut((size_t)T + 1);
+    for (int t = 0; t <= T; ++t) cut[t] = R * t / T;
+    parallel_for_threads(T, [&](int t) { std::sort(sel.begin() + cut[t], sel.begin() + cut[t + 1], less); });
+    for (int w = 1; w < T; w *= 2) {
+      const int nm = (T + 2 * w - 1) / (2 * w), nt = std::min(nm, std::max(nthreads, 1));
+      parallel_for_threads(nt, [&](int tid) {
+        for (int m = tid; m < nm; m += nt) {
+          const int a0 = 2 * w * m, a1 = std::min(T, a0 + w), a2 = std::min(T, a0 + 2 * w);
+          if (a1 < a2) std::inplace_merge(sel.begin() + cut[a0], sel.begin() + cut[a1], sel.begin() + cut[a2], less);
+        }
+      });
+    }
+  }
+  const int64_t keep = limit >= 0 ? std::min(limit, R) : R;
+  out->ante_off.resize((size_t)keep + 1);
+  for (int64_t i = 0; i < keep; ++i) out->ante_off[(size_t)i + 1] = out->ante_off[(size_t)i] + sel[(size_t)i].msz;
+  out->ante.resize((size_t)out->ante_off[(size_t)keep]);
+  for (auto* v : {&out->cS, &out->cA, &out->cC}) v->resize((size_t)keep);
+  for (auto* v : {&out->support, &out->conf, &out->lift, &out->leverage, &out->conviction}) v->resize((size_t)keep);
+  out->cons.resize((size_t)keep);
+  parallel_for(keep, nthreads, 4096, [&](int64_t b, int64_t e, int) {
+    for (int64_t i = b; i < e; ++i) {
+      const Sel& r = sel[(size_t)i];
+      const int32_t* a = rows_all + base[r.msz] + (int64_t)r.aidx * r.msz;
+      std::copy(a, a + r.msz, out->ante.begin() + out->ante_off[(size_t)i]);
+      out->cons[i] = r.cons;
+      out->cS[i] = r.cS; out->cA[i] = r.cA; out->cC[i] = r.cC;
+      out->support[i] = rm_support(r.cS, N);
+      out->conf[i] = rm_confidence(r.cS, r.cA);
+      out->lift[i] = rm_lift(r.cS, r.cA, r.cC, N);
+      out->leverage[i] = rm_leverage(r.cS, r.cA, r.cC, N);
+      out->conviction[i] = rm_conviction(r.cS, r.cA, r.cC, N);
+    }
+  });
+  *n_rules = keep;
+  return out;
+}
+
+FA_API int64_t fa_rule_measures_nante(RuleMeasureSet* h) { return (int64_t)h->ante.size(); }
+
+// every array holds R elements (ante_off R+1, ante fa_rule_measures_nante)
+FA_API void fa_rule_measures_export(RuleMeasureSet* h, int64_t* ante_off, int32_t* ante, int32_t* cons, int64_t* cS,
+                                    int64_t* cA, int64_t* cC, double* support, double* conf, double* lift,
+                                    double* leverage, double* conviction) {
+  auto put = [](auto* dst, const auto& v) {
+    if (!v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(v[0]));
+  };
+  put(ante_off, h->ante_off); put(ante, h->ante); put(cons, h->cons);
+  put(cS, h->cS); put(cA, h->cA); put(cC, h->cC);
+  put(support, h->support); put(conf, h->conf); put(lift, h->lift);
+  put(leverage, h->leverage); put(conviction, h->conviction);
+}
+
+FA_API void fa_rule_measures_free(RuleMeasureSet* h) { delete h; }

@@ -42,6 +42,18 @@ void fa_recommend_cpu(const int64_t* ante_off, const int32_t* ante, const int32_
 int fa_write_freq_itemsets(const char* path, const char* tokbuf, const int64_t* tokoff, int32_t F1,
                            const int32_t* const* rows, const int64_t* const* counts, const int64_t* sizes,
                            int levels, int with_counts, int nthreads);
+void* fa_rule_measures_cpu(const int32_t* rows_all, const int64_t* base, const int64_t* cnt_all, const int64_t* cbase,
+                           int K, int64_t N, double min_conf, int has_lift, double min_lift, int sort, int64_t limit,
+                           const int64_t* tie_pos, int nthreads, int64_t* n_rules);
+int64_t fa_rule_measures_nante(void* h);
+void fa_rule_measures_export(void* h, int64_t* ante_off, int32_t* ante, int32_t* cons, int64_t* cS, int64_t* cA,
+                             int64_t* cC, double* support, double* conf, double* lift, double* leverage,
+                             double* conviction);
+void fa_rule_measures_free(void* h);
+int fa_write_rules(const char* path, const char* tokbuf, const int64_t* tokoff, const int64_t* ante_off,
+                   const int32_t* ante, const int32_t* cons, const int64_t* cS, const int64_t* cA, const int64_t* cC,
+                   const double* support, const double* conf, const double* lift, const double* leverage,
+                   const double* conviction, int64_t R, int nthreads);
 void fa_cpu_histogram(const int32_t* items, int64_t nnz, int64_t V, int64_t* out, int nthreads);
 void fa_cpu_build_bitmaps(const int64_t* roff, const int32_t* ranks, const int32_t* src, int64_t ncols, int64_t Wp,
                           uint64_t* bm, int nthreads);
@@ -362,6 +374,79 @@ static void test_rules_edges(int nt) {
   }
 }
 
+// The rule export (fa_rule_measures_cpu, fa_write_rules): all pairs of 200 items plus a few
+// triples, so several chunks of itemsets and of written rules run on the pool; every sort,
+// a threshold, a limit; then inputs with a missing antecedent or consequent, which are
+// errors and must not index a level with -1 (the sanitizers watch).
+static void test_rule_measures(int nt) {
+  const int32_t F1 = 200;
+  const int64_t N = 100000;
+  std::vector<int32_t> rows;
+  std::vector<int64_t> cnt, tie(F1);
+  for (int32_t i = 0; i < F1; ++i) rows.push_back(i), cnt.push_back(N - 17 * i), tie[i] = F1 - 1 - i;
+  for (int32_t i = 0; i < F1; ++i)
+    for (int32_t j = i + 1; j < F1; ++j) rows.push_back(i), rows.push_back(j), cnt.push_back(N / 2 - 13 * i - 7 * j);
+  const int64_t n2 = (int64_t)F1 * (F1 - 1) / 2, n3 = 50;
+  for (int32_t i = 0; i < n3; ++i) rows.push_back(i), rows.push_back(i + 1), rows.push_back(i + 2), cnt.push_back(1000 + i);
+  const int64_t base[5] = {0, 0, F1, F1 + 2 * n2, F1 + 2 * n2 + 3 * n3}, cbase[4] = {0, F1, F1 + n2, F1 + n2 + n3};
+  const int64_t all = 2 * n2 + 3 * n3;
+  std::string tokbuf;
+  std::vector<int64_t> tokoff{0};
+  for (int32_t i = 0; i < F1; ++i) tokbuf += "t" + std::to_string(i), tokoff.push_back((int64_t)tokbuf.size());
+  for (int sort = 0; sort < 5; ++sort) {
+    int64_t R = -1;
+    void* h = fa_rule_measures_cpu(rows.data(), base, cnt.data(), cbase, 3, N, 0.0, 0, 0.0, sort, -1, tie.data(), nt, &R);
+    CHECK(R == all && fa_rule_measures_nante(h) == 2 * n2 + 6 * n3);
+    std::vector<int64_t> aoff(R + 1), cS(R), cA(R), cC(R);
+    std::vector<int32_t> ante(fa_rule_measures_nante(h)), cons(R);
+    std::vector<double> m[5];
+    for (auto& v : m) v.resize(R);
+    fa_rule_measures_export(h, aoff.data(), ante.data(), cons.data(), cS.data(), cA.data(), cC.data(), m[0].data(),
+                            m[1].data(), m[2].data(), m[3].data(), m[4].data());
+    fa_rule_measures_free(h);
+    const std::vector<double>& key = m[sort == 0 ? 1 : sort == 1 ? 2 : sort == 2 ? 3 : sort == 3 ? 4 : 0];
+    for (int64_t r = 1; r < R; ++r) CHECK(key[r - 1] >= key[r]);
+    for (int64_t r = 0; r < R; ++r) CHECK(m[1][r] == (double)cS[r] / (double)cA[r] && m[0][r] == (double)cS[r] / (double)N);
+    if (sort == 1) {
+      const char* path = "/tmp/fa_selftest_rules.txt";
+      CHECK(fa_write_rules(path, tokbuf.data(), tokoff.data(), aoff.data(), ante.data(), cons.data(), cS.data(),
+                           cA.data(), cC.data(), m[0].data(), m[1].data(), m[2].data(), m[3].data(), m[4].data(), R,
+                           nt) == 0);
+      FILE* f = std::fopen(path, "rb");
+      CHECK(f != nullptr);
+      if (f) {
+        int64_t lines = 0, tabs = 0;
+        for (int ch; (ch = std::fgetc(f)) != EOF;) lines += ch == '\n', tabs += ch == '\t';
+        std::fclose(f);
+        CHECK(lines == R && tabs == 9 * R);
+        std::remove(path);
+      }
+    }
+  }
+  int64_t R = -1, Rl = -1;
+  void* h = fa_rule_measures_cpu(rows.data(), base, cnt.data(), cbase, 3, N, 0.4, 1, 1.0, 2, -1, tie.data(), nt, &R);
+  fa_rule_measures_free(h);
+  CHECK(R >= 0 && R < all);
+  h = fa_rule_measures_cpu(rows.data(), base, cnt.data(), cbase, 3, N, 0.4, 1, 1.0, 2, 5, tie.data(), nt, &Rl);
+  fa_rule_measures_free(h);
+  CHECK(Rl == std::min<int64_t>(R, 5));
+  {  // {0, 1, 2} without {1, 2} in level 2; {0, 2} without {2} in level 1
+    const int32_t r[] = {0, 1, 2, 0, 1, 0, 2, 0, 1, 2};
+    const int64_t c[] = {5, 4, 3, 3, 2, 2}, b3[5] = {0, 0, 3, 7, 10}, cb3[4] = {0, 3, 5, 6}, t3[3] = {2, 0, 1};
+    h = fa_rule_measures_cpu(r, b3, c, cb3, 3, 10, 0.0, 0, 0.0, 0, -1, t3, nt, &R);
+    CHECK(R == -3 && fa_rule_measures_nante(h) == 0);
+    fa_rule_measures_free(h);
+    const int32_t r2[] = {0, 1, 0, 1, 0, 2};
+    const int64_t c2[] = {5, 4, 3, 2}, b2[4] = {0, 0, 2, 6}, cb2[3] = {0, 2, 4};
+    h = fa_rule_measures_cpu(r2, b2, c2, cb2, 2, 10, 0.0, 0, 0.0, 0, -1, t3, nt, &R);
+    CHECK(R == -2);
+    fa_rule_measures_free(h);
+    h = fa_rule_measures_cpu(r2, b2, c2, cb2, 1, 10, 0.0, 0, 0.0, 0, -1, t3, nt, &R);     // level 1 only
+    CHECK(R == 0);
+    fa_rule_measures_free(h);
+  }
+}
+
 // The slab rule (fa_slab.h) at hand-computed points; tests/test_slab_rule.py sweeps it.
 static void test_slab_rule() {
   const double lds = 163328;
@@ -403,6 +488,7 @@ int main(int argc, char** argv) {
   test_apriori_gen(nt);
   test_kernels_and_rules(nt);
   test_rules_edges(nt);
+  test_rule_measures(nt);
   if (g_fail) {
     std::fprintf(stderr, "%d check(s) failed\n", g_fail);
     return 1;

@@ -6,6 +6,8 @@
 // pure-ASCII vocabularies that is plain byte order; otherwise every line is
 // compared through its UTF-16 image.
 #include <algorithm>
+#include <charconv>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 
@@ -36,6 +38,50 @@ static void utf8_to_utf16be(const char* s, size_t n, std::string& out) {
     }
     i += len;
   }
+}
+
+// Python's repr(float): the shortest decimal that round-trips (std::to_chars' digits),
+// laid out by repr's rule -- fixed notation for decimal exponents -4..15 with a trailing
+// ".0" on integers, else d[.ddd]e[+-]XX with an exponent of at least two digits; inf, -inf
+// and nan by name.  Appends to out.
+static void repr_double(double v, std::string& out) {
+  if (v != v) { out += "nan"; return; }
+  if (v < 0 || (v == 0 && std::signbit(v))) { out.push_back('-'); v = -v; }
+  if (v > 1.7976931348623157e308) { out += "inf"; return; }
+  char buf[40];
+  const auto r = std::to_chars(buf, buf + sizeof buf, v, std::chars_format::scientific);
+  // d[.ddd]e[+-]XX[X]: the digits without the point, and the exponent
+  char dig[24];
+  int nd = 0, e = 0;
+  const char* p = buf;
+  for (; p < r.ptr && *p != 'e'; ++p)
+    if (*p != '.') dig[nd++] = *p;
+  if (p < r.ptr) {
+    ++p;
+    const bool neg = *p == '-';
+    if (*p == '-' || *p == '+') ++p;
+    for (; p < r.ptr; ++p) e = e * 10 + (*p - '0');
+    if (neg) e = -e;
+  }
+  if (e >= -4 && e < 16) {
+    if (e >= 0) {
+      for (int i = 0; i <= e; ++i) out.push_back(i < nd ? dig[i] : '0');
+      out.push_back('.');
+      if (nd > e + 1) out.append(dig + e + 1, (size_t)(nd - e - 1)); else out.push_back('0');
+    } else {
+      out += "0.";
+      out.append((size_t)(-e - 1), '0');
+      out.append(dig, (size_t)nd);
+    }
+    return;
+  }
+  out.push_back(dig[0]);
+  if (nd > 1) { out.push_back('.'); out.append(dig + 1, (size_t)(nd - 1)); }
+  out.push_back('e');
+  out.push_back(e < 0 ? '-' : '+');
+  const int ae = e < 0 ? -e : e;
+  if (ae < 10) out.push_back('0');
+  out += std::to_string(ae);
 }
 
 }  // namespace fa
@@ -163,4 +209,46 @@ FA_API int fa_write_freq_itemsets(const char* path, const char* tokbuf, const in
   const size_t wrote = n ? std::fwrite(out.data(), 1, (size_t)ooff[n], f) : 0;
   const int rc = std::fclose(f);
   return (rc == 0 && wrote == (size_t)ooff[n]) ? 0 : 2;
+}
+
+// The exported rules (AssociationRules.all_rules), one per line in table order:
+//   antecedent tokens (rank-descending, one space apart) \t consequent token \t cS \t cA
+//   \t cC \t support \t confidence \t lift \t leverage \t conviction
+// with every float as Python's repr() writes it.  Tokens hold no tab: the parser splits on
+// whitespace.  Chunks of rules are formatted in parallel and written in order.
+FA_API int fa_write_rules(const char* path, const char* tokbuf, const int64_t* tokoff, const int64_t* ante_off,
+                          const int32_t* ante, const int32_t* cons, const int64_t* cS, const int64_t* cA,
+                          const int64_t* cC, const double* support, const double* conf, const double* lift,
+                          const double* leverage, const double* conviction, int64_t R, int nthreads) {
+  constexpr int64_t kChunk = 4096;
+  const int64_t nchunks = (R + kChunk - 1) / kChunk;
+  std::vector<std::string> text((size_t)nchunks);
+  parallel_for(nchunks, nthreads, 1, [&](int64_t b, int64_t e, int) {
+    for (int64_t c = b; c < e; ++c) {
+      std::string& o = text[(size_t)c];
+      for (int64_t i = c * kChunk; i < std::min(R, (c + 1) * kChunk); ++i) {
+        for (int64_t j = ante_off[i + 1] - 1; j >= ante_off[i]; --j) {   // ascending ranks: emit descending
+          o.append(tokbuf + tokoff[ante[j]], (size_t)(tokoff[ante[j] + 1] - tokoff[ante[j]]));
+          if (j > ante_off[i]) o.push_back(' ');
+        }
+        o.push_back('\t');
+        o.append(tokbuf + tokoff[cons[i]], (size_t)(tokoff[cons[i] + 1] - tokoff[cons[i]]));
+        for (const int64_t v : {cS[i], cA[i], cC[i]}) {
+          o.push_back('\t');
+          o += std::to_string((long long)v);
+        }
+        for (const double v : {support[i], conf[i], lift[i], leverage[i], conviction[i]}) {
+          o.push_back('\t');
+          repr_double(v, o);
+        }
+        o.push_back('\n');
+      }
+    }
+  });
+  FILE* f = std::fopen(path, "wb");
+  if (!f) return 1;
+  bool ok = true;
+  for (const std::string& t : text) ok = ok && (t.empty() || std::fwrite(t.data(), 1, t.size(), f) == t.size());
+  const int rc = std::fclose(f);
+  return (rc == 0 && ok) ? 0 : 2;
 }

@@ -86,6 +86,11 @@ class JobConfig:
     top_n_scores: bool = False                  # ... every entry as token:confidence
     closed: bool = False                        # also write <out>closedItemset ("a b[cnt]": no superset of equal count)
     maximal: bool = False                       # also write <out>maximalItemset ("a b[cnt]": no frequent superset)
+    rules: bool = False                         # also write <out>rules (every rule with its measures, no cut)
+    min_confidence: float = 0.0                 # ... keeping confidence >= this
+    min_lift: float | None = None               # ... and lift >= this
+    rules_sort: str = "confidence"              # ... ordered by this measure, descending
+    rules_limit: int | None = None              # ... the first K only
     extra: dict = field(default_factory=dict)
 
 
@@ -133,7 +138,22 @@ def build_parser() -> argparse.ArgumentParser:
                    help="also write <output>maximalItemset/: the frequent itemsets with no frequent proper superset, "
                         "as 'a b c[count]' lines. With --max-level L: maximal among the itemsets of at most L items "
                         "(every level-L itemset is written)")
+    p.add_argument("--rules", action="store_true",
+                   help="also write <output>rules/: every rule 'A -> c' with A + {c} frequent (no redundancy cut), one "
+                        "per line, tab-separated: antecedent tokens, consequent, count(A+c), count(A), count(c), "
+                        "support, confidence, lift, leverage, conviction. Needs the full result and the line total "
+                        "(with --rules-only: a complete checkpoint)")
+    p.add_argument("--min-confidence", type=float, default=None, metavar="F",
+                   help="with --rules: keep rules with confidence >= F (default 0)")
+    p.add_argument("--min-lift", type=float, default=None, metavar="F", help="with --rules: also require lift >= F")
+    p.add_argument("--rules-sort", choices=list(RULE_SORTS), default=None,
+                   help="with --rules: the measure the file is ordered by, descending (default confidence)")
+    p.add_argument("--rules-limit", type=int, default=None, metavar="K", help="with --rules: the first K rules only")
     return p
+
+
+# --rules-sort's choices; a measure's position is its code in csrc/host/fa_rule_measures.h (RuleSort)
+RULE_SORTS = ("confidence", "lift", "leverage", "conviction", "support")
 
 
 def parse_args(argv=None) -> JobConfig:
@@ -143,10 +163,18 @@ def parse_args(argv=None) -> JobConfig:
         p.error(f"--top-n {a.top_n}: N must be in 1..64")
     if a.top_n_scores and not a.top_n:
         p.error("--top-n-scores requires --top-n")
+    for flag, v in (("--min-confidence", a.min_confidence), ("--min-lift", a.min_lift),
+                    ("--rules-sort", a.rules_sort), ("--rules-limit", a.rules_limit)):
+        if v is not None and not a.rules:
+            p.error(f"{flag} requires --rules")
+    if a.rules_limit is not None and a.rules_limit < 0:
+        p.error(f"--rules-limit {a.rules_limit}: K must not be negative")
     warn_unread_env()
     return JobConfig(input=a.input, output=a.output, temp=a.temp, min_support=a.min_support, device=a.device,
                      dedup=a.dedup, pair_strategy=a.pair_strategy, with_counts=a.with_counts, resume=a.resume,
                      rules_only=a.rules_only, checkpoint=a.checkpoint, overwrite=a.overwrite,
                      profile=a.profile, metrics_path=a.metrics_path, max_level=a.max_level,
                      strategy=a.strategy, world_size=a.world_size, tiebreak=a.tiebreak, top_n=a.top_n,
-                     top_n_scores=a.top_n_scores, closed=a.closed, maximal=a.maximal)
+                     top_n_scores=a.top_n_scores, closed=a.closed, maximal=a.maximal, rules=a.rules,
+                     min_confidence=0.0 if a.min_confidence is None else a.min_confidence, min_lift=a.min_lift,
+                     rules_sort=a.rules_sort or "confidence", rules_limit=a.rules_limit)

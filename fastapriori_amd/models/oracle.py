@@ -139,6 +139,36 @@ def sort_rules(rules, items: list[str]):
                                         tuple(sorted(t[0]))))
 
 
+def all_rules(res: OracleResult, min_confidence: float = 0.0, min_lift: float | None = None,
+              sort: str = "confidence", limit: int | None = None) -> list[tuple]:
+    """The rule export by brute force (an extension: the reference never shows its rules):
+    every rule A -> c with A + {c} frequent and at least two items, NO cut, as
+    (A, c, cS, cA, cC, support, confidence, lift, leverage, conviction).  Python ints for the
+    products and differences, one float division per measure; the counts are the stored ones
+    (level 1: occurrences).  Kept: confidence >= min_confidence and lift >= min_lift; order:
+    the sort measure descending, confidence descending, the consequent's tiebreak key,
+    antecedent size, antecedent ranks."""
+    n = res.n_lines
+    if n <= 0:
+        raise ValueError("all_rules: the line total is unknown")
+    out = []
+    for s, cs in res.itemsets.items():
+        if len(s) < 2:
+            continue
+        for c in s:
+            a = s - {c}
+            ca, cc = res.itemsets[a], res.itemsets[frozenset([c])]
+            m = {"support": float(cs) / float(n), "confidence": float(cs) / float(ca),
+                 "lift": float(cs * n) / float(ca * cc), "leverage": float(cs * n - ca * cc) / float(n * n),
+                 "conviction": float("inf") if ca == cs else float(ca * (n - cc)) / float(n * (ca - cs))}
+            if m["confidence"] >= min_confidence and (min_lift is None or m["lift"] >= min_lift):
+                out.append((a, c, cs, ca, cc, m["support"], m["confidence"], m["lift"], m["leverage"], m["conviction"],
+                            m[sort]))
+    tie = [rule_tiebreak_key(t) for t in res.items]
+    out.sort(key=lambda t: (-t[10], -t[6], tie[t[1]], len(t[0]), tuple(sorted(t[0]))))
+    return [t[:10] for t in (out if limit is None else out[:limit])]
+
+
 def recommend(res: OracleResult, user_lines: list[list[str]]) -> list[str]:
     rules = sort_rules(gen_rules(res), res.items)
     rank = {t: i for i, t in enumerate(res.items)}

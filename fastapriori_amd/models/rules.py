@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..ops.host import RuleTable, rules_build
+from ..ops.host import RuleMeasures, RuleTable, rule_measures, rules_build
 from ..parallel.comm import Comm
 from ..utils.jvm import rule_tiebreak_key
 from ..utils.metrics import Logger
@@ -51,12 +51,17 @@ class AssociationRules:
         self.use_index = True      # per-item rule lists for big rule tables (k_recommend_indexed)
 
     # ------------------------------------------------------------------
+    def _tie_pos(self) -> np.ndarray:
+        """Position of every rank's token in the consequent tiebreak order."""
+        items = self.result.items
+        order = sorted(range(len(items)), key=lambda r: rule_tiebreak_key(items[r]))
+        tie_pos = np.empty(len(items), dtype=np.int64)
+        tie_pos[np.asarray(order, dtype=np.int64)] = np.arange(len(items), dtype=np.int64)
+        return tie_pos
+
     def rules(self) -> RuleTable:
         if self._rules is None:
-            items = self.result.items
-            order = sorted(range(len(items)), key=lambda r: rule_tiebreak_key(items[r]))
-            tie_pos = np.empty(len(items), dtype=np.int64)
-            tie_pos[np.asarray(order, dtype=np.int64)] = np.arange(len(items), dtype=np.int64)
+            tie_pos = self._tie_pos()
             if self.device.type == "cuda":
                 d = ops.primitives.rules_build_device(self.result.levels, self.result.counts, tie_pos, self.device)
                 self._rules = RuleTable(d["ante_off"].cpu().numpy(), d["ante"].cpu().numpy(),
@@ -75,6 +80,31 @@ class AssociationRules:
                 self.log.metric(phase="rule_cut", level=size, before=before, after=after, ms=round(t, 3))
             self.log.line(f"Size association rules {self._rules.n_rules}")
         return self._rules
+
+    def all_rules(self, min_confidence: float = 0.0, min_lift: float | None = None, sort: str = "confidence",
+                  limit: int | None = None) -> RuleMeasures:
+        """The rule export (an extension; the reference never shows its rules): EVERY rule
+        A -> c with A + {c} frequent and at least two items -- the cut serves the recommender
+        only and stays in rules() -- with support, confidence, lift, leverage and conviction
+        (csrc/host/fa_rule_measures.h: exact int64 products of the stored counts, one fp64
+        division; level-1 counts are occurrence counts, so with repeated tokens on a line
+        count(c) can exceed the line total and leverage / conviction go negative).
+
+        Kept: confidence >= min_confidence and, when given, lift >= min_lift (fp64, bounds
+        inclusive).  Order: ``sort`` (confidence, lift, leverage, conviction or support)
+        descending with +inf first, then confidence descending, the consequent's tie
+        position, antecedent size, antecedent row; ``limit`` keeps that many rules.
+        Takes the full mined result: a condensed one is not downward closed and raises
+        RuntimeError, as any result with a subset missing from the level below; ValueError
+        when the line total is unknown or it or a count exceeds 2^31 - 1.  A GPU rank
+        runs ops.primitives.rule_measures_device, a CPU rank ops.host.rule_measures."""
+        r = self.result
+        args = (min_confidence, min_lift, sort, limit)
+        if self.device.type == "cuda":
+            d = ops.primitives.rule_measures_device(r.levels, r.counts, r.n_lines, self._tie_pos(), self.device, *args)
+            return RuleMeasures(*[d[k].cpu().numpy() for k in ("ante_off", "ante", "cons", "cnt_s", "cnt_a", "cnt_c",
+                                                               "support", "conf", "lift", "leverage", "conviction")])
+        return rule_measures(r.levels, r.counts, r.n_lines, self._tie_pos(), *args)
 
     def rule_list(self) -> list[tuple[tuple[int, ...], int, float]]:
         rt = self.rules()

@@ -67,6 +67,11 @@ _HOST_SIGS = {
     "fa_rules_nstats": (i64, [vp]),
     "fa_rules_export": (None, [vp, vp, vp, vp, vp, vp]),
     "fa_rules_free": (None, [vp]),
+    "fa_rule_measures_cpu": (vp, [vp, vp, vp, vp, C.c_int, i64, dbl, C.c_int, dbl, C.c_int, i64, vp, C.c_int, vp]),
+    "fa_rule_measures_nante": (i64, [vp]),
+    "fa_rule_measures_export": (None, [vp] * 12),
+    "fa_rule_measures_free": (None, [vp]),
+    "fa_write_rules": (C.c_int, [cp, cp] + [vp] * 12 + [i64, C.c_int]),
     "fa_recommend_cpu": (None, [vp, vp, vp, i64, i32, vp, vp, i64, vp, C.c_int]),
     "fa_recommend_topn_cpu": (None, [vp, vp, vp, i64, i32, vp, vp, i64, i32, vp, C.c_int]),
     "fa_condense_cpu": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, vp, C.c_int]),
@@ -160,6 +165,12 @@ _HIP_SIGS = {
     "fa_hip_rule_gen": (C.c_int, [vp, i64, C.c_int, vp, i64, vp, vp, vp, vp, vp, vp]),
     "fa_hip_rule_cut": (C.c_int, [vp, vp, i64, C.c_int, vp, vp, vp, vp]),
     "fa_hip_rule_emit": (C.c_int, [vp, vp, vp, vp, vp, i64, vp, vp]),
+    # the rule export (rules.hip k_rm_*): selection + count, emission, the kept rules' measures
+    "fa_hip_rule_measures": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, i64, dbl, C.c_int, dbl, C.c_int, vp, vp, vp,
+                                       vp, vp]),
+    "fa_hip_rule_measures_emit": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, i64, C.c_int, vp, vp, i64, vp, vp, vp,
+                                            vp, vp, vp, vp, vp, vp]),
+    "fa_hip_rule_measures_fin": (C.c_int, [vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp]),
     "fa_hip_sup_mark": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]),
 }
 

@@ -6,6 +6,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
+from ..config import RULE_SORTS          # in fa_rule_measures.h RuleSort's order
 from ..utils.env import num_threads
 from . import _native
 
@@ -46,6 +47,113 @@ class RuleTable:
 
     def antecedent(self, i: int) -> np.ndarray:
         return self.ante[self.ante_off[i]:self.ante_off[i + 1]]
+
+
+@dataclass
+class RuleMeasures:
+    """The exported rules (AssociationRules.all_rules): every rule A -> c of every frequent
+    S = A + {c}, without the cut, in the chosen order, with its three stored counts and five
+    measures (csrc/host/fa_rule_measures.h; level-1 counts are occurrence counts)."""
+    ante_off: np.ndarray    # int64 [R+1]
+    ante: np.ndarray        # int32 concatenated antecedent ranks (ascending)
+    cons: np.ndarray        # int32 [R]
+    cnt_s: np.ndarray       # int64 [R] count(A + {c})
+    cnt_a: np.ndarray       # int64 [R] count(A)
+    cnt_c: np.ndarray       # int64 [R] count({c})
+    support: np.ndarray     # float64 [R] cS / N
+    conf: np.ndarray        # float64 [R] cS / cA
+    lift: np.ndarray        # float64 [R] cS N / (cA cC)
+    leverage: np.ndarray    # float64 [R] (cS N - cA cC) / N^2
+    conviction: np.ndarray  # float64 [R] cA (N - cC) / (N (cA - cS)), +inf when cA == cS
+
+    @property
+    def n_rules(self) -> int:
+        return int(self.cons.size)
+
+    def antecedent(self, i: int) -> np.ndarray:
+        return self.ante[self.ante_off[i]:self.ante_off[i + 1]]
+
+
+RULE_COUNT_MAX = 2 ** 31 - 1                                               # ... kRuleCountMax
+
+
+def rule_measures_plan(levels, counts, n_lines, min_confidence, min_lift, sort, limit) -> dict:
+    """What both export paths (rule_measures here, ops.primitives.rule_measures_device) start
+    from: the checked arguments and the levels in condense_marks' layout.
+
+    Raises ValueError for an unknown line total (``n_lines <= 0``: a result reloaded from
+    ``freqItems`` files), for a line total or a count above 2^31 - 1 (the measures' int64
+    products are exact up to there) or below 1, and for bad options; RuntimeError
+    (rules_not_closed) for rows above an empty level.  The levels end at the first empty one."""
+    if sort not in RULE_SORTS:
+        raise ValueError(f"all_rules: sort must be one of {', '.join(RULE_SORTS)}, not {sort!r}")
+    if limit is not None and limit < 0:
+        raise ValueError(f"all_rules: limit = {limit} is negative")
+    n_lines = int(n_lines)
+    if n_lines <= 0:
+        raise ValueError("all_rules: the line total is unknown (n_lines = 0: a result loaded from freqItems files "
+                         "carries none; a complete checkpoint does), so support, lift, leverage and conviction "
+                         "are undefined")
+    if n_lines > RULE_COUNT_MAX:
+        raise ValueError(f"all_rules: {n_lines} lines exceed the limit of 2^31 - 1 = {RULE_COUNT_MAX} "
+                         "(the measures' int64 products are exact up to there)")
+    sizes = [len(c) for c in counts]
+    bad = rules_gap_level([len(l) for l in levels])
+    if bad:
+        raise rules_not_closed(bad)
+    K = 0
+    while K < len(levels) and sizes[K] > 0:
+        K += 1
+    lv = [np.ascontiguousarray(levels[k], dtype=np.int32).reshape(-1) for k in range(K)]
+    ct = [np.ascontiguousarray(counts[k], dtype=np.int64).reshape(-1) for k in range(K)]
+    if any(l.size != c.size * (k + 1) for k, (l, c) in enumerate(zip(lv, ct))):
+        raise ValueError("all_rules: levels[k-1] must be [n_k, k] with n_k counts")
+    for c in ct:
+        if c.size and (int(c.max()) > RULE_COUNT_MAX or int(c.min()) < 1):
+            raise ValueError(f"all_rules: a count of {int(c.max()) if int(c.max()) > RULE_COUNT_MAX else int(c.min())} "
+                             f"is outside 1 .. 2^31 - 1 = {RULE_COUNT_MAX} (the measures' int64 products are "
+                             "exact up to there)")
+    sizes = np.array(sizes[:K] or [0], dtype=np.int64)
+    base = np.zeros(K + 2, dtype=np.int64)            # base[m]: element offset of the size-m level
+    np.cumsum([l.size for l in lv], out=base[2:K + 2])
+    cbase = np.zeros(K + 1, dtype=np.int64)           # cbase[m-1]: first row of the size-m level
+    np.cumsum(sizes[:K], out=cbase[1:])
+    eoff = np.zeros(K + 2, dtype=np.int64)            # eoff[k]: first (itemset, position) index of level k >= 2
+    for k in range(2, K + 1):
+        eoff[k + 1] = eoff[k] + int(sizes[k - 1]) * k
+    return dict(K=K, sizes=sizes, base=base, cbase=cbase, eoff=eoff, n=int(cbase[K]), N=n_lines,
+                rows=np.concatenate(lv) if lv else np.zeros(0, dtype=np.int32),
+                cnts=np.concatenate(ct) if ct else np.zeros(0, dtype=np.int64),
+                min_conf=float(min_confidence), has_lift=int(min_lift is not None),
+                min_lift=float(min_lift) if min_lift is not None else 0.0, sort=RULE_SORTS.index(sort),
+                limit=-1 if limit is None else int(limit))
+
+
+def rule_measures(levels: list[np.ndarray], counts: list[np.ndarray], n_lines: int, tie_pos: np.ndarray,
+                  min_confidence: float = 0.0, min_lift: float | None = None, sort: str = "confidence",
+                  limit: int | None = None) -> RuleMeasures:
+    """The rule export on the CPU (csrc/host/rules.cpp fa_rule_measures_cpu): selection,
+    order and errors as ops.primitives.rule_measures_device; see rule_measures_plan."""
+    m = rule_measures_plan(levels, counts, n_lines, min_confidence, min_lift, sort, limit)
+    tie = np.ascontiguousarray(tie_pos, dtype=np.int64)
+    if tie.size == 0:
+        tie = np.zeros(1, dtype=np.int64)
+    nr = np.zeros(1, dtype=np.int64)
+    lib = _native.host()
+    h = lib.fa_rule_measures_cpu(m["rows"].ctypes.data, m["base"].ctypes.data, m["cnts"].ctypes.data,
+                                 m["cbase"].ctypes.data, m["K"], m["N"], m["min_conf"], m["has_lift"], m["min_lift"],
+                                 m["sort"], m["limit"], tie.ctypes.data, num_threads(), nr.ctypes.data)
+    R = int(nr[0])
+    if R < 0:
+        lib.fa_rule_measures_free(h)
+        raise rules_not_closed(-R)
+    na = int(lib.fa_rule_measures_nante(h))
+    ante_off, ante, cons = np.zeros(R + 1, dtype=np.int64), np.zeros(na, dtype=np.int32), np.zeros(R, dtype=np.int32)
+    ints = [np.zeros(R, dtype=np.int64) for _ in range(3)]
+    flts = [np.zeros(R, dtype=np.float64) for _ in range(5)]
+    lib.fa_rule_measures_export(h, *[a.ctypes.data for a in (ante_off, ante, cons, *ints, *flts)])
+    lib.fa_rule_measures_free(h)
+    return RuleMeasures(ante_off, ante, cons, *ints, *flts)
 
 
 def rules_not_closed(bad: int) -> RuntimeError:

@@ -25,7 +25,7 @@ import torch
 from ..tuning import TUNING
 from ..utils.env import num_threads
 from . import _native
-from .host import rules_gap_level, rules_not_closed
+from .host import rule_measures_plan, rules_gap_level, rules_not_closed
 
 _I32, _I64 = torch.int32, torch.int64
 PAIR_CHUNK_ROWS = 1 << 18   # rows per pair-kernel chunk (working set ~10 MB: L2 / Infinity Cache resident)
@@ -1456,6 +1456,106 @@ def rules_build_device(levels: list, counts: list, tie_pos: np.ndarray, dev) -> 
                   "fa_hip_rule_emit")
     return dict(ante_off=ante_off, ante=ante, cons=cons_r[o].contiguous(), conf=conf_r[o].contiguous(),
                 level_stats=stats, level_ms=level_ms)
+
+
+RULE_TPB = 256      # rules.hip kRuleTPB: (itemset, position) elements per workgroup of the export
+
+
+def rule_measures_device(levels: list, counts: list, n_lines: int, tie_pos: np.ndarray, dev,
+                         min_confidence: float = 0.0, min_lift: float | None = None, sort: str = "confidence",
+                         limit: int | None = None) -> dict:
+    """The rule export on the GPU (csrc/hip/rules.hip k_rm_*; no counterpart in the reference):
+    every rule A -> c of every frequent S = A + {c}, |S| >= 2, without the cut.
+
+    levels / counts as rules_build_device, checked by ops.host.rule_measures_plan.  One upload,
+    then one dispatch sequence whatever the number of levels: fa_hip_rule_measures selects on
+    the thresholds and counts (one thread per (S, position) over all levels, per-workgroup
+    totals, one scan), the selected count R and the error word come back in ONE readback, and
+    fa_hip_rule_measures_emit writes only the R selected rules, stably and without atomics.
+    torch stable sorts order them (sort measure desc, confidence desc, consequent tie
+    position, antecedent size, antecedent row: a total order), ``limit`` keeps a prefix, and
+    fa_hip_rule_measures_fin / fa_hip_rule_emit write the kept rules' five measures and
+    antecedent rows.  Returns tensors on ``dev``: ante_off int64 [R+1], ante int32, cons int32,
+    cnt_s / cnt_a / cnt_c int64, support / conf / lift / leverage / conviction float64.
+
+    A subset missing from the level below (or a consequent missing from level 1) raises
+    RuntimeError naming the level through the error word, before anything is ordered."""
+    m = rule_measures_plan(levels, counts, n_lines, min_confidence, min_lift, sort, limit)
+    dev = torch.device(dev)
+    K, N = m["K"], m["N"]
+    f64 = torch.float64
+
+    def result(ante_off, ante, cons, ints, flts):
+        return dict(ante_off=ante_off, ante=ante, cons=cons, cnt_s=ints[0], cnt_a=ints[1], cnt_c=ints[2],
+                    support=flts[0], conf=flts[1], lift=flts[2], leverage=flts[3], conviction=flts[4])
+
+    def empty():
+        return result(torch.zeros(1, dtype=_I64, device=dev), torch.zeros(0, dtype=_I32, device=dev),
+                      torch.zeros(0, dtype=_I32, device=dev), [torch.zeros(0, dtype=_I64, device=dev) for _ in range(3)],
+                      [torch.zeros(0, dtype=f64, device=dev) for _ in range(5)])
+
+    total = int(m["eoff"][K + 1]) if K >= 2 else 0
+    nwg = (total + RULE_TPB - 1) // RULE_TPB
+    lib = _native.hip()
+    rows_all = torch.from_numpy(m["rows"]).to(dev)
+    n = m["n"]
+    tab = torch.from_numpy(np.concatenate([m["cnts"], m["base"], m["cbase"], m["eoff"]])).to(dev)
+    p0 = tab.data_ptr()
+    p_base, p_cbase, p_eoff = p0 + 8 * n, p0 + 8 * (n + K + 2), p0 + 8 * (n + 2 * K + 3)
+    st = _stream(rows_all)
+    sub = torch.empty(max(total, 1), dtype=_I32, device=dev)
+    wgtot = torch.empty(max(nwg, 1), dtype=_I32, device=dev)
+    wgoff = torch.empty(max(nwg, 1), dtype=_I64, device=dev)
+    ctl = torch.zeros(2, dtype=_I64, device=dev)             # [0]: selected rules R, [1]: error level
+    rc = lib.fa_hip_rule_measures(_p(rows_all), p_base, p0, p_cbase, p_eoff, m["sizes"].ctypes.data, K, N,
+                                  m["min_conf"], m["has_lift"], m["min_lift"], m["sort"], _p(sub), _p(wgtot),
+                                  _p(wgoff), _p(ctl), st)
+    if rc == 3:
+        raise RuntimeError("fa_hip_rule_measures: a level has 2^31 - 1 rows or more (the subset index is int32)")
+    _native.check(rc, "fa_hip_rule_measures")
+    if total == 0:
+        return empty()                                       # the launcher returned before any launch
+    R, bad = ctl.tolist()                                    # the one readback before the sort
+    if bad:
+        raise rules_not_closed(int(bad))
+    if R == 0:
+        return empty()
+    ints = [torch.empty(R, dtype=_I64, device=dev) for _ in range(3)]
+    msz, aidx, cons = (torch.empty(R, dtype=_I32, device=dev) for _ in range(3))
+    conf, key = torch.empty(R, dtype=f64, device=dev), torch.empty(R, dtype=f64, device=dev)
+    _native.check(lib.fa_hip_rule_measures_emit(_p(rows_all), p_base, p0, p_cbase, p_eoff, m["sizes"].ctypes.data, K, N,
+                                                m["sort"], _p(sub), _p(wgoff), R, _p(ints[0]), _p(ints[1]),
+                                                _p(ints[2]), _p(msz), _p(aidx), _p(cons), _p(conf), _p(key), st),
+                  "fa_hip_rule_measures_emit")
+    del sub
+    tie = torch.from_numpy(np.ascontiguousarray(tie_pos, dtype=np.int64)).to(dev)[cons.to(_I64)]
+    # total order, least significant key first: antecedent (size, row), consequent tie
+    # position, confidence desc, the sort measure desc (+inf first)
+    okey = (msz.to(_I64) << 32) | aidx.to(_I64)
+    if len(tie_pos) < (1 << 24) and K < 128:
+        o = torch.argsort(okey | (tie << 39))
+    else:
+        o = torch.argsort(okey)
+        o = o[torch.argsort(tie[o], stable=True)]
+    o = o[torch.sort(conf[o], descending=True, stable=True)[1]]
+    if m["sort"] != 0:
+        o = o[torch.sort(key[o], descending=True, stable=True)[1]]
+    if m["limit"] >= 0:
+        o = o[:m["limit"]]
+    Rk = int(o.numel())
+    if Rk == 0:
+        return empty()
+    ints = [c[o].contiguous() for c in ints]
+    msz_s, idx_s = msz[o].contiguous(), aidx[o].contiguous()
+    flts = [torch.empty(Rk, dtype=f64, device=dev) for _ in range(5)]
+    _native.check(lib.fa_hip_rule_measures_fin(_p(ints[0]), _p(ints[1]), _p(ints[2]), Rk, N, *[_p(f) for f in flts],
+                                               st), "fa_hip_rule_measures_fin")
+    ante_off = torch.zeros(Rk + 1, dtype=_I64, device=dev)
+    torch.cumsum(msz_s.to(_I64), 0, out=ante_off[1:])
+    ante = torch.empty(int(ante_off[-1].item()), dtype=_I32, device=dev)
+    _native.check(lib.fa_hip_rule_emit(_p(rows_all), p_base, _p(msz_s), _p(idx_s), _p(ante_off), Rk, _p(ante), st),
+                  "fa_hip_rule_emit")
+    return result(ante_off, ante, cons[o].contiguous(), ints, flts)
 
 
 def condense_marks(levels: list, counts: list, dev, check: bool = True) -> dict:

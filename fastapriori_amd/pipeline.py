@@ -161,6 +161,32 @@ def condense_window(cfg: JobConfig, comm, log: Logger, result, summary: dict) ->
         summary[f"n_{kind}"] = n_kept
 
 
+def rules_window(cfg: JobConfig, comm, log: Logger, result, summary: dict) -> None:
+    """--rules (no counterpart in the reference): after condense_window and before the
+    recommendation window, so neither of the reference's timed windows gets slower.  Every
+    rank holds the identical result: rank 0 alone computes AssociationRules.all_rules on its
+    device and writes ``<output>rules`` (io.write_rules); the others meet it where it
+    reports how that went, and a failure raises on every rank."""
+    t0 = time.perf_counter()
+    n, err = None, None
+    if comm.is_root:
+        try:
+            ar = AssociationRules(result, comm, Logger(enabled=False))
+            rm = ar.all_rules(cfg.min_confidence, cfg.min_lift, cfg.rules_sort, cfg.rules_limit)
+            io.write_rules(rm, result.items, cfg.output + "rules", overwrite=cfg.overwrite)
+            n = rm.n_rules
+        except (OSError, RuntimeError, ValueError) as e:
+            err = f"{type(e).__name__}: {e}"
+    n, err = comm.broadcast_object((n, err))                   # the ranks' meeting point
+    if err:
+        raise RuntimeError(f"--rules failed on rank 0: {err}")
+    ms = int((time.perf_counter() - t0) * 1000)
+    log.line(f"Total time for get rules {ms}")
+    log.metric(phase="rules_export", n_rules=n, min_confidence=cfg.min_confidence, min_lift=cfg.min_lift,
+               sort=cfg.rules_sort, limit=cfg.rules_limit, ms=ms)
+    summary["n_rules_exported"] = n
+
+
 def make_checkpointer(cfg: JobConfig, comm) -> Checkpointer | None:
     if cfg.temp and (cfg.checkpoint or cfg.rules_only):
         # rules-only needs no D.dat: it reloads the mined itemsets (Utils.getAll's use case)
@@ -204,6 +230,8 @@ def run_job(cfg: JobConfig, comm=None) -> dict:
 
         if cfg.closed or cfg.maximal:
             condense_window(cfg, comm, log, result, summary)
+        if cfg.rules:
+            rules_window(cfg, comm, log, result, summary)
 
         t2 = time.time()
         recommend_window(cfg, comm, log, result, summary)

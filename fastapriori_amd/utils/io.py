@@ -364,6 +364,30 @@ def write_freq_itemsets(result: MiningResult, out_dir: str, with_counts: bool = 
     return part
 
 
+def write_rules(rules, items: list[str], out_dir: str, overwrite: bool = False) -> str:
+    """``<output>rules/part-00000`` (no counterpart in the reference): the exported rules
+    (ops.host.RuleMeasures) in table order, one per line, tab-separated:
+
+        antecedent tokens, rank-descending, one space apart <TAB> consequent token <TAB>
+        cS <TAB> cA <TAB> cC <TAB> support <TAB> confidence <TAB> lift <TAB> leverage <TAB> conviction
+
+    Floats are the shortest decimals that round-trip, byte-equal to Python's repr()
+    (``inf`` / ``-inf``); csrc/host/writer.cpp fa_write_rules."""
+    _prepare_dir(out_dir, overwrite)
+    blob, off = _tokens_blob(items)
+    part = os.path.join(out_dir, "part-00000")
+    arrs = [np.ascontiguousarray(a, dtype=t) for a, t in
+            ((rules.ante_off, np.int64), (rules.ante, np.int32), (rules.cons, np.int32), (rules.cnt_s, np.int64),
+             (rules.cnt_a, np.int64), (rules.cnt_c, np.int64), (rules.support, np.float64), (rules.conf, np.float64),
+             (rules.lift, np.float64), (rules.leverage, np.float64), (rules.conviction, np.float64))]
+    rc = _native.host().fa_write_rules(part.encode(), blob, off.ctypes.data, *[a.ctypes.data for a in arrs],
+                                       rules.n_rules, num_threads())
+    if rc:
+        raise OSError(f"failed to write {part}")
+    open(os.path.join(out_dir, "_SUCCESS"), "wb").close()
+    return part
+
+
 def write_lines(lines: list[str], out_dir: str, overwrite: bool = False) -> str:
     """``<output>recommends/part-00000``: one token per U.dat line (Utils.scala:43-49)."""
     _prepare_dir(out_dir, overwrite)
