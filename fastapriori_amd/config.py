@@ -91,6 +91,9 @@ class JobConfig:
     min_lift: float | None = None               # ... and lift >= this
     rules_sort: str = "confidence"              # ... ordered by this measure, descending
     rules_limit: int | None = None              # ... the first K only
+    count_itemsets: str | None = None           # query file: also write <out>itemsetCounts ("a b[cnt]" per query line)
+    count_only: bool = False                    # ... and end there: no mining, no U.dat, no checkpoint
+    verify_counts: bool = False                 # recount every mined itemset of >= 2 items over D.dat and compare
     extra: dict = field(default_factory=dict)
 
 
@@ -149,6 +152,16 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--rules-sort", choices=list(RULE_SORTS), default=None,
                    help="with --rules: the measure the file is ordered by, descending (default confidence)")
     p.add_argument("--rules-limit", type=int, default=None, metavar="K", help="with --rules: the first K rules only")
+    p.add_argument("--count-itemsets", metavar="PATH", default=None,
+                   help="also write <output>itemsetCounts/: for every line of the query file PATH (tokenised as a "
+                        "D.dat line; a blank line is the empty token) the number of D.dat lines that contain all of "
+                        "its tokens, as 'a b c[count]' with the line's distinct tokens in first-occurrence order. A "
+                        "line count: a token repeated inside a D.dat line counts once")
+    p.add_argument("--count-only", action="store_true",
+                   help="with --count-itemsets: read D.dat, count, write and end (no mining, no U.dat, no checkpoint)")
+    p.add_argument("--verify-counts", action="store_true",
+                   help="after mining, recount every mined itemset of two or more items over D.dat with the query "
+                        "counter, which shares nothing with the miner, and fail on the first difference")
     return p
 
 
@@ -169,6 +182,14 @@ def parse_args(argv=None) -> JobConfig:
             p.error(f"{flag} requires --rules")
     if a.rules_limit is not None and a.rules_limit < 0:
         p.error(f"--rules-limit {a.rules_limit}: K must not be negative")
+    if a.count_only and not a.count_itemsets:
+        p.error("--count-only requires --count-itemsets")
+    for flag, on in (("--count-itemsets", a.count_itemsets), ("--count-only", a.count_only),
+                     ("--verify-counts", a.verify_counts)):
+        if on and a.rules_only:
+            p.error(f"{flag} cannot be combined with --rules-only (there is no database to count over)")
+    if a.verify_counts and a.count_only:
+        p.error("--verify-counts cannot be combined with --count-only (nothing is mined)")
     warn_unread_env()
     return JobConfig(input=a.input, output=a.output, temp=a.temp, min_support=a.min_support, device=a.device,
                      dedup=a.dedup, pair_strategy=a.pair_strategy, with_counts=a.with_counts, resume=a.resume,
@@ -177,4 +198,5 @@ def parse_args(argv=None) -> JobConfig:
                      strategy=a.strategy, world_size=a.world_size, tiebreak=a.tiebreak, top_n=a.top_n,
                      top_n_scores=a.top_n_scores, closed=a.closed, maximal=a.maximal, rules=a.rules,
                      min_confidence=0.0 if a.min_confidence is None else a.min_confidence, min_lift=a.min_lift,
-                     rules_sort=a.rules_sort or "confidence", rules_limit=a.rules_limit)
+                     rules_sort=a.rules_sort or "confidence", rules_limit=a.rules_limit,
+                     count_itemsets=a.count_itemsets, count_only=a.count_only, verify_counts=a.verify_counts)

@@ -206,6 +206,15 @@ def recommend_topn(res: OracleResult, user_lines: list[list[str]], n: int) -> li
     return out
 
 
+def count_itemsets(lines: list[list[str]], queries: list[list[str]]) -> list[int]:
+    """Support of given itemsets by brute force (an extension: the reference counts only
+    what it mines): per query the number of lines that contain every one of its tokens.  A
+    LINE count -- a token repeated inside a line counts once, unlike the level-1 counts
+    of ``mine`` -- with Python sets and nothing else."""
+    sets = [set(toks) for toks in lines]
+    return [sum(1 for s in sets if q <= s) for q in (set(q) for q in queries)]
+
+
 def freq_itemset_lines(res: OracleResult) -> list[str]:
     """``Utils.saveFreqItemset``: tokens rank-descending, lines in Java String order."""
     lines = [" ".join(res.items[r] for r in sorted(s, reverse=True)) for s in res.itemsets]

@@ -61,6 +61,16 @@ _HOST_SIGS = {
     "fa_dl_layout": (cp, [C.c_int, I64P]),
     # the kernels' capacity limits and pads by name (csrc/host/fa_limits.h)
     "fa_limits": (cp, [C.c_int, I64P]),
+    # the query counter's limits and LDS rule by name (csrc/host/fa_query.h), its window plan and
+    # the C++ reference on the launcher's inputs (csrc/host/query.cpp)
+    "fa_query_limits": (cp, [C.c_int, I64P]),
+    "fa_query_lds_bytes": (i64, [i64, i64, i64]),
+    "fa_query_width": (C.c_int, [i64, i64, i64]),
+    "fa_query_plan": (vp, [vp, vp, vp, i64, i64, i64, i64]),
+    "fa_query_plan_info": (None, [vp, vp]),
+    "fa_query_plan_export": (None, [vp, vp, vp, vp, vp, vp]),
+    "fa_query_plan_free": (None, [vp]),
+    "fa_query_count_cpu": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, C.c_int]),
     "fa_f1_rank_numeric": (i64, [vp, i64, i64, vp, vp, vp]),
     "fa_rules_build": (vp, [vp, vp, vp, C.c_int, vp, C.c_int, vp]),
     "fa_rules_nante": (i64, [vp]),
@@ -172,6 +182,8 @@ _HIP_SIGS = {
                                             vp, vp, vp, vp, vp, vp]),
     "fa_hip_rule_measures_fin": (C.c_int, [vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp]),
     "fa_hip_sup_mark": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]),
+    # the query counter (query.hip k_query_slab): window descriptors on the host and on the device
+    "fa_hip_query_count": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, i64, C.c_int, vp]),
 }
 
 

@@ -1875,6 +1875,115 @@ def limits() -> _NativeTable:
     return _NativeTable(_native.host().fa_limits)
 
 
+@functools.lru_cache(maxsize=None)
+def query_limits() -> _NativeTable:
+    """csrc/host/fa_query.h (fa_query_limits): the query counter's limits."""
+    return _NativeTable(_native.host().fa_query_limits)
+
+
+def query_window_lds(n_items: int, sw: int, n_q: int) -> int:
+    """fa_query.h's LDS footprint of a window: slab, accumulators and tile offsets."""
+    return int(_native.host().fa_query_lds_bytes(int(n_items), int(sw), int(n_q)))
+
+
+def query_width(n_items: int, n_q: int, lds: int) -> int:
+    """The widest slab (words of 64 rows) of a window within ``lds`` bytes; 0: none fits."""
+    return int(_native.host().fa_query_width(int(n_items), int(n_q), int(lds)))
+
+
+# fields of a window descriptor (fa_query.h QWin), in order
+QUERY_WIN_FIELDS = ("n_q", "n_items", "sw", "tab_off", "qoff_off", "qrow_off", "q_base", "reserved")
+
+
+def query_plan(qoff: np.ndarray, qidx: np.ndarray, index: np.ndarray, n_used: int, n_queries: int,
+               acc: int | None = None, lds: int | None = None) -> dict:
+    """The window plan of the query counter (csrc/host/query.cpp fa_query_plan).
+
+    ``qoff`` / ``qidx``: the LIVE queries as a CSR of used indices in [0, n_used), distinct
+    and ascending inside a query; ``index[i]``: query i's place in the count vector of
+    ``n_queries`` entries (dead queries have no place in the plan and stay 0).  ``acc``:
+    queries per window (TUNING.query_acc, 0 = kQAcc), ``lds``: a window's LDS bytes
+    (TUNING.query_lds_bytes).  Returns the plan's host tensors: wins int64 [W, 8]
+    (QUERY_WIN_FIELDS), tab uint16 [W * n_used], qoff int32, qrow uint16, perm int64, and
+    n_queries / n_used / lds.  ValueError when one query alone exceeds a window at width 1."""
+    L = query_limits()
+    acc = int(TUNING.query_acc if acc is None else acc) or L.kQAcc
+    lds = int(TUNING.query_lds_bytes if lds is None else lds)
+    if not 1 <= acc <= L.kQAcc:
+        raise ValueError(f"query_plan: {acc} queries per window is outside 1..{L.kQAcc} (kQAcc)")
+    if not 0 < lds <= L.kQLdsMax:
+        raise ValueError(f"query_plan: {lds} LDS bytes is outside 1..{L.kQLdsMax} (kQLdsMax)")
+    qoff = np.ascontiguousarray(qoff, dtype=np.int64)
+    qidx = np.ascontiguousarray(qidx, dtype=np.int32)
+    index = np.ascontiguousarray(index, dtype=np.int64)
+    Q = len(qoff) - 1
+    assert len(index) == Q and (Q == 0 or int(qoff[-1]) == len(qidx))
+    lib = _native.host()
+    h = lib.fa_query_plan(qoff.ctypes.data, qidx.ctypes.data, index.ctypes.data, Q, int(n_used), acc, lds)
+    try:
+        info = np.zeros(8, dtype=np.int64)
+        lib.fa_query_plan_info(h, info.ctypes.data)
+        err, bad, bad_len, cap1, W, n_tab, n_qoff, n_qrow = (int(v) for v in info)
+        if err:
+            raise ValueError(f"query {bad} has {bad_len} distinct items: a window holds at most {cap1} at width 1 "
+                             f"(kQMaxItems = {L.kQMaxItems} slab rows, {lds} LDS bytes)")
+        wins = np.zeros((W, len(QUERY_WIN_FIELDS)), dtype=np.int64)
+        tab = np.zeros(max(n_tab, 1), dtype=np.uint16)
+        qo = np.zeros(max(n_qoff, 1), dtype=np.int32)
+        qr = np.zeros(max(n_qrow, 1), dtype=np.uint16)
+        perm = np.zeros(max(Q, 1), dtype=np.int64)
+        lib.fa_query_plan_export(h, wins.ctypes.data, tab.ctypes.data, qo.ctypes.data, qr.ctypes.data,
+                                 perm.ctypes.data)
+    finally:
+        lib.fa_query_plan_free(h)
+    return {"wins": torch.from_numpy(wins), "tab": torch.from_numpy(tab), "qoff": torch.from_numpy(qo),
+            "qrow": torch.from_numpy(qr), "perm": torch.from_numpy(perm), "n_queries": int(n_queries),
+            "n_used": int(n_used), "lds": lds}
+
+
+def query_count(offsets: torch.Tensor, items: torch.Tensor, lut: torch.Tensor, plan: dict, max_wg: int | None = None,
+                windows: tuple[int, int] | None = None) -> torch.Tensor:
+    """Lines of the CSR shard (``offsets`` int64 [n + 1], ``items`` int32 raw ids, distinct per
+    line) that hold every item of each planned query -> int64 [n_queries] on the shard's
+    device, query order.  ``lut``: int32 raw id -> used index (-1: in no query), on the
+    shard's device.  A device shard runs query.hip's k_query_slab in one launch (``max_wg``
+    workgroups, 0 / None: TUNING.query_max_wg, then the launcher's rule), a CPU shard the C++
+    reference: there is no fallback from one to the other.  ``windows`` = (r, n) counts only
+    the windows w with w % n == r (the other queries stay 0)."""
+    assert offsets.dtype == _I64 and items.dtype == _I32 and lut.dtype == _I32
+    assert offsets.is_contiguous() and items.is_contiguous() and lut.is_contiguous()
+    dev = items.device
+    assert offsets.device == dev and lut.device == dev
+    n_rows = offsets.numel() - 1
+    out = torch.zeros(max(plan["n_queries"], 1), dtype=_I64, device=dev)
+    wins = plan["wins"]
+    if windows is not None:
+        wins = wins[windows[0]::windows[1]].contiguous()
+    W = int(wins.shape[0])
+    if W == 0 or n_rows <= 0:
+        return out[:plan["n_queries"]]
+    max_wg = int(TUNING.query_max_wg if max_wg is None else max_wg)
+    if dev.type == "cuda":
+        key = ("dev", str(dev))
+        if key not in plan:       # the plan's tables go to a device once
+            plan[key] = {k: plan[k].to(dev) for k in ("tab", "qoff", "qrow", "perm")}
+        d = plan[key]
+        wins_dev = wins.to(dev)
+        rc = _native.hip().fa_hip_query_count(_p(offsets), _p(items), n_rows, _p(lut), lut.numel(), _p(wins),
+                                              _p(wins_dev), W, _p(d["tab"]), _p(d["qoff"]), _p(d["qrow"]),
+                                              _p(d["perm"]), _p(out), plan["lds"], max_wg, _stream(items))
+        if rc == 3:
+            raise ValueError("fa_hip_query_count: arguments outside the query counter's limits (fa_query.h)")
+        _native.check(rc, "fa_hip_query_count")
+    else:
+        rc = _native.host().fa_query_count_cpu(_p(offsets), _p(items), n_rows, _p(lut), lut.numel(), _p(wins), W,
+                                               _p(plan["tab"]), _p(plan["qoff"]), _p(plan["qrow"]),
+                                               _p(plan["perm"]), _p(out), plan["lds"], num_threads())
+        if rc == 3:
+            raise ValueError("fa_query_count_cpu: arguments outside the query counter's limits (fa_query.h)")
+    return out[:plan["n_queries"]]
+
+
 class _DlLayout(_NativeTable):
     """csrc/host/fa_dl.h (fa_dl_layout): the control block's slots (kDlStop ..), the limits
     and the slab count's mode bits; desc_dtype, the level table's record type (DlDesc);

@@ -132,6 +132,66 @@ def recommend_window(cfg: JobConfig, comm, log: Logger, result, summary: dict) -
     return recs
 
 
+def count_window(cfg: JobConfig, comm, log: Logger, result, summary: dict) -> None:
+    """--count-itemsets / --verify-counts (no counterpart in the reference): after the
+    mining window and before condense_window, so neither of the reference's timed windows
+    gets slower.  It reads D.dat itself, as mine_window does and with the same --strategy
+    (mine_window keeps nothing of its shard), and counts with models.query.count_itemsets,
+    which shares nothing with the miner.
+
+    --count-itemsets PATH: rank 0 reads the query file and sends the queries to every
+    rank, all ranks count, rank 0 writes ``<output>itemsetCounts`` -- line i: query line
+    i's distinct tokens in first-occurrence order, one space apart, then ``[count]`` -- and
+    the others meet it where it reports how that went.  --verify-counts: every mined
+    itemset of two or more items is recounted and compared with the mined count (level 1
+    counts occurrences, the query counter lines: docs/PARITY.md); the vectors are identical
+    on every rank, so a difference raises on every rank."""
+    from .models.query import ItemsetQueries, count_itemsets, result_counts
+    t0 = time.perf_counter()
+    whole = Comm(device=comm.device)
+    shard = io.read_shard(cfg.input + "D.dat", comm if cfg.strategy == "count" else whole)
+    if cfg.count_itemsets:
+        queries, err = None, None
+        if comm.is_root:
+            try:
+                queries = ItemsetQueries.from_file(cfg.count_itemsets)
+            except (OSError, RuntimeError, ValueError) as e:
+                err = f"{type(e).__name__}: {e}"
+        queries, err = comm.broadcast_object((queries, err))
+        if err:
+            raise RuntimeError(f"--count-itemsets: reading {cfg.count_itemsets} failed on rank 0: {err}")
+        counts = count_itemsets(shard, queries, comm, cfg.strategy)
+        n, err = None, None
+        if comm.is_root:
+            try:
+                lines = [" ".join(queries.query_tokens(i)) + f"[{c}]" for i, c in enumerate(counts.tolist())]
+                io.write_lines(lines, cfg.output + "itemsetCounts", overwrite=cfg.overwrite)
+                n = len(lines)
+            except (OSError, RuntimeError, ValueError) as e:
+                err = f"{type(e).__name__}: {e}"
+        n, err = comm.broadcast_object((n, err))                   # the ranks' meeting point
+        if err:
+            raise RuntimeError(f"--count-itemsets failed on rank 0: {err}")
+        ms = int((time.perf_counter() - t0) * 1000)
+        log.line(f"Total time for get itemsetCounts {ms}")
+        log.metric(phase="count_itemsets", n_queries=n, ms=ms)
+        summary["n_counted"] = n
+    if cfg.verify_counts:
+        t1 = time.perf_counter()
+        queries = ItemsetQueries.from_result(result, min_size=2)
+        got = count_itemsets(shard, queries, comm, cfg.strategy)
+        want = result_counts(result, min_size=2)
+        bad = (got != want).nonzero()[0]
+        if len(bad):
+            i = int(bad[0])
+            raise RuntimeError(f"--verify-counts: itemset {{{' '.join(queries.query_tokens(i))}}} was mined with count "
+                               f"{int(want[i])} but {int(got[i])} lines of D.dat contain it "
+                               f"({len(bad)} of {len(want)} itemsets differ)")
+        log.line(f"verified {len(want)} itemset counts")
+        log.metric(phase="verify_counts", n_verified=len(want), ms=int((time.perf_counter() - t1) * 1000))
+        summary["n_verified"] = len(want)
+
+
 CONDENSED_DIRS = {"closed": "closedItemset", "maximal": "maximalItemset"}
 
 
@@ -188,7 +248,7 @@ def rules_window(cfg: JobConfig, comm, log: Logger, result, summary: dict) -> No
 
 
 def make_checkpointer(cfg: JobConfig, comm) -> Checkpointer | None:
-    if cfg.temp and (cfg.checkpoint or cfg.rules_only):
+    if cfg.temp and (cfg.checkpoint or cfg.rules_only) and not cfg.count_only:
         # rules-only needs no D.dat: it reloads the mined itemsets (Utils.getAll's use case)
         fp = None if cfg.rules_only else input_fingerprint(cfg.input + "D.dat", cfg.min_support)
         return Checkpointer(cfg.temp, comm.rank, fp)
@@ -211,6 +271,13 @@ def run_job(cfg: JobConfig, comm=None) -> dict:
         ckpt = make_checkpointer(cfg, comm)
         comm.barrier()
 
+        if cfg.count_only:
+            # --count-itemsets PATH --count-only: D.dat is read, counted and written; nothing is mined
+            count_window(cfg, comm, log, None, summary)
+            summary.update(world_size=comm.world_size)
+            log.metric(phase="job", **{k: v for k, v in summary.items() if not isinstance(v, dict)})
+            return summary
+
         t1 = time.time()
         if cfg.rules_only:
             # the complete checkpoint under temp, else the saved result files of a
@@ -228,6 +295,8 @@ def run_job(cfg: JobConfig, comm=None) -> dict:
         t_mine = int((time.time() - t1) * 1000)
         log.line(f"Total time for get freqItemsets {t_mine}")
 
+        if cfg.count_itemsets or cfg.verify_counts:
+            count_window(cfg, comm, log, result, summary)
         if cfg.closed or cfg.maximal:
             condense_window(cfg, comm, log, result, summary)
         if cfg.rules:

@@ -100,6 +100,10 @@ class Tuning:
     # when the binomial estimate keeps fewer than this share of the rows, or of the items
     trim_rows_frac: float = 0.75
     trim_nnz_frac: float = 0.6
+    # ---- the query counter (ops/primitives.py query_plan / query_count) -------------
+    query_lds_bytes: int = 160 * 1024 - 512   # LDS of a window: slab, accumulators, tile offsets (fa_query.h)
+    query_acc: int = 0                  # queries per window (0: fa_query.h kQAcc; smaller makes more windows)
+    query_max_wg: int = 0               # workgroups of the one launch (0: the launcher's rule)
     # ---- I/O (utils/io.py) -------------------------------------------------------
     gpu_parse: bool = True              # D.dat parsed on the GPU behind the H2D copies
     gpu_parse_dict: bool = True         # dictionary-mode tokens too
