@@ -258,6 +258,56 @@ FA_API void fa_recommend_topn_cpu(const int64_t* ante_off, const int32_t* ante, 
   });
 }
 
+// Leave-one-out rank on the CPU (an extension, AssociationRules.evaluate): trial t is
+// element t of the basket CSR, trow[t] its row.  out[t] = the 1-based place of h = bask[t]
+// in the top-n list (fa_recommend_topn_cpu's) of its basket without h, 0 when it is not in
+// it.  Written as the definition: clear h's bit, walk the table in order, restore the bit.
+// 1 <= n.  Device counterpart: csrc/hip/recommend.hip k_holdout_rank(_indexed).
+FA_API void fa_holdout_rank_cpu(const int64_t* ante_off, const int32_t* ante, const int32_t* cons,
+                                int64_t R, int32_t F1, const int64_t* bask_off, const int32_t* bask,
+                                const int64_t* trow, int64_t T, int32_t n, int32_t* out, int nthreads) {
+  const int64_t words = ((int64_t)F1 + 63) / 64;
+  parallel_for(T, nthreads, 256, [&](int64_t b, int64_t e, int) {
+    std::vector<uint64_t> bits((size_t)std::max<int64_t>(1, words), 0), taken(bits.size(), 0);
+    std::vector<int32_t> got;
+    int64_t cur = -1;                                  // the row whose bits are set
+    auto unset = [&]() {
+      if (cur >= 0)
+        for (int64_t i = bask_off[cur]; i < bask_off[cur + 1]; ++i) bits[bask[i] >> 6] = 0;
+    };
+    for (int64_t t = b; t < e; ++t) {
+      const int64_t u = trow[t];
+      if (u != cur) {
+        unset();
+        cur = u;
+        for (int64_t i = bask_off[u]; i < bask_off[u + 1]; ++i) bits[bask[i] >> 6] |= 1ull << (bask[i] & 63);
+      }
+      const int32_t h = bask[t];
+      const int64_t usz = bask_off[u + 1] - bask_off[u] - 1;
+      bits[h >> 6] &= ~(1ull << (h & 63));
+      int32_t rank = 0;
+      got.clear();
+      for (int64_t r = 0; r < R && usz > 0 && (int32_t)got.size() < n; ++r) {
+        const int32_t c = cons[r];
+        if (((bits[c >> 6] | taken[c >> 6]) >> (c & 63)) & 1) continue;
+        const int64_t a0 = ante_off[r], a1 = ante_off[r + 1];
+        if (a1 - a0 > usz) continue;
+        bool sub = true;
+        for (int64_t i = a0; i < a1; ++i)
+          if (!((bits[ante[i] >> 6] >> (ante[i] & 63)) & 1)) { sub = false; break; }
+        if (!sub) continue;
+        taken[c >> 6] |= 1ull << (c & 63);
+        got.push_back(c);
+        if (c == h) { rank = (int32_t)got.size(); break; }
+      }
+      for (int32_t c : got) taken[c >> 6] = 0;
+      bits[h >> 6] |= 1ull << (h & 63);
+      out[t] = rank;
+    }
+    unset();
+  });
+}
+
 // ---------------------------------------------------------------------------
 // Rule export (AssociationRules.all_rules; no counterpart in the reference): every rule
 // A -> c of every frequent S = A + {c}, |S| >= 2, WITHOUT the cut, with the measures of

@@ -10,4 +10,4 @@ __version__ = "0.1.0"
 from .models.apriori import FastApriori, MinerConfig, mine  # noqa: F401,E402
 from .models.data import MiningResult, TransactionShard, Vocabulary  # noqa: F401,E402
 from .models.query import ItemsetQueries, count_itemsets  # noqa: F401,E402
-from .models.rules import AssociationRules  # noqa: F401,E402
+from .models.rules import AssociationRules, Evaluation  # noqa: F401,E402

@@ -94,6 +94,8 @@ class JobConfig:
     count_itemsets: str | None = None           # query file: also write <out>itemsetCounts ("a b[cnt]" per query line)
     count_only: bool = False                    # ... and end there: no mining, no U.dat, no checkpoint
     verify_counts: bool = False                 # recount every mined itemset of >= 2 items over D.dat and compare
+    evaluate: int = 0                           # > 0: also write <out>evaluation (leave-one-out metrics of the top-N lists)
+    evaluate_ranks: bool = False                # ... and <out>evaluationRanks (token:rank per U.dat line)
     extra: dict = field(default_factory=dict)
 
 
@@ -162,6 +164,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--verify-counts", action="store_true",
                    help="after mining, recount every mined itemset of two or more items over D.dat with the query "
                         "counter, which shares nothing with the miner, and fail on the first difference")
+    p.add_argument("--evaluate", type=int, default=0, metavar="N",
+                   help="also write <output>evaluation/: leave-one-out evaluation of the top-N (1..64) recommender on "
+                        "U.dat itself, one JSON line: every item of every basket of two or more frequent items is "
+                        "hidden in turn and ranked in the top-N list of the rest; hit rate@1..N, MRR and NDCG")
+    p.add_argument("--evaluate-ranks", action="store_true",
+                   help="with --evaluate: also write <output>evaluationRanks/: per U.dat line token:rank for every "
+                        "frequent item of the line (0 = not in the list), or 0 when the line has none")
     return p
 
 
@@ -188,6 +197,13 @@ def parse_args(argv=None) -> JobConfig:
                      ("--verify-counts", a.verify_counts)):
         if on and a.rules_only:
             p.error(f"{flag} cannot be combined with --rules-only (there is no database to count over)")
+    if a.evaluate != 0 and not 1 <= a.evaluate <= 64:
+        p.error(f"--evaluate {a.evaluate}: N must be in 1..64")
+    if a.evaluate_ranks and not a.evaluate:
+        p.error("--evaluate-ranks requires --evaluate")
+    for flag, on in (("--evaluate", a.evaluate), ("--evaluate-ranks", a.evaluate_ranks)):
+        if on and a.count_only:
+            p.error(f"{flag} cannot be combined with --count-only (nothing is mined)")
     if a.verify_counts and a.count_only:
         p.error("--verify-counts cannot be combined with --count-only (nothing is mined)")
     warn_unread_env()
@@ -199,4 +215,5 @@ def parse_args(argv=None) -> JobConfig:
                      top_n_scores=a.top_n_scores, closed=a.closed, maximal=a.maximal, rules=a.rules,
                      min_confidence=0.0 if a.min_confidence is None else a.min_confidence, min_lift=a.min_lift,
                      rules_sort=a.rules_sort or "confidence", rules_limit=a.rules_limit,
-                     count_itemsets=a.count_itemsets, count_only=a.count_only, verify_counts=a.verify_counts)
+                     count_itemsets=a.count_itemsets, count_only=a.count_only, verify_counts=a.verify_counts,
+                     evaluate=a.evaluate, evaluate_ranks=a.evaluate_ranks)

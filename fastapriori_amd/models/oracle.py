@@ -206,6 +206,32 @@ def recommend_topn(res: OracleResult, user_lines: list[list[str]], n: int) -> li
     return out
 
 
+def holdout_ranks(res: OracleResult, user_lines: list[list[str]], n: int) -> list[list[tuple[str, int]]]:
+    """Leave-one-out ranks per line (an extension: the reference evaluates nothing): for every
+    item h of the line's basket (its distinct frequent items), in rank order, (token, the
+    1-based position of h in the top-n list of the basket without h, or 0).  A basket of
+    fewer than two items has no trial: its item, if any, gets 0."""
+    rules = sort_rules(gen_rules(res), res.items)
+    rank = {t: i for i, t in enumerate(res.items)}
+    out = []
+    for toks in user_lines:
+        u = frozenset(rank[t] for t in toks if t in rank)
+        line = []
+        for h in sorted(u):
+            rest, seen, pos = u - {h}, set(), 0
+            for a, r, _ in rules:
+                if len(u) < 2 or len(seen) == n:
+                    break
+                if r not in rest and r not in seen and a <= rest:
+                    seen.add(r)
+                    if r == h:
+                        pos = len(seen)
+                        break
+            line.append((res.items[h], pos))
+        out.append(line)
+    return out
+
+
 def count_itemsets(lines: list[list[str]], queries: list[list[str]]) -> list[int]:
     """Support of given itemsets by brute force (an extension: the reference counts only
     what it mines): per query the number of lines that contain every one of its tokens.  A

@@ -19,6 +19,8 @@ Reference: AssociationRules.scala (class AssociationRules, :17-190).
   collect to driver + saveRecommends                 gather of rank ids to rank 0
   (none: the scan stops at the first match)          ranked top-N lists with confidences (run_topn):
                                                      HIP k_recommend_topn / k_recommend_topn_indexed
+  (none: nothing is evaluated)                       leave-one-out hit rate / MRR / NDCG (evaluate):
+                                                     HIP k_holdout_rank / k_holdout_rank_indexed
 
 Divergences (documented): when there are no rules at all the reference throws
 on ``rules.keys.min`` (:147); we recommend "0" for every user.  Non-integer
@@ -26,6 +28,10 @@ consequent tokens in a confidence tie would throw NumberFormatException there;
 we order them after the integers by Java string order.
 """
 from __future__ import annotations
+
+import json
+import math
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -36,6 +42,47 @@ from ..parallel.comm import Comm
 from ..utils.jvm import rule_tiebreak_key
 from ..utils.metrics import Logger
 from .data import MiningResult, TransactionShard, Vocabulary, hash_tokens
+
+
+@dataclass
+class Evaluation:
+    """Leave-one-out evaluation of the top-n recommender over a U.dat (AssociationRules.evaluate;
+    the definitions are in docs/PARITY.md).  A trial hides one item of a basket of at least
+    two items and ranks it in the top-n list of the rest; ``hits[r - 1]`` counts the trials of
+    rank r.  The integers are summed over all ranks first, so the floats do not depend on the
+    world size: sums over r ascending in float64, one division by ``n_trials`` at the end."""
+    n: int
+    n_lines: int
+    n_lines_skipped: int           # lines with fewer than two frequent items: no trial
+    n_trials: int
+    n_infrequent_tokens: int       # occurrences of tokens that are no frequent item
+    hits: list[int]
+    hit_rate: list[float]          # hit_rate[k - 1]: trials of rank 1..k over all trials
+    mrr: float
+    ndcg: float
+
+    @classmethod
+    def from_counts(cls, n: int, n_lines: int, n_lines_skipped: int, n_trials: int, n_infrequent_tokens: int,
+                    hits: list[int]) -> "Evaluation":
+        hits = [int(h) for h in hits]
+        assert len(hits) == n
+        cum, rr, dcg, acc = [], 0.0, 0.0, 0
+        for r, h in enumerate(hits, 1):
+            acc += h
+            cum.append(acc)
+            rr += h / r
+            dcg += h / math.log2(r + 1)
+        T = int(n_trials)
+        if T == 0:
+            rate, rr, dcg = [0.0] * n, 0.0, 0.0
+        else:
+            rate, rr, dcg = [c / T for c in cum], rr / T, dcg / T
+        return cls(int(n), int(n_lines), int(n_lines_skipped), T, int(n_infrequent_tokens), hits, rate, rr, dcg)
+
+    def as_json(self) -> str:
+        """One JSON object, keys in field order, floats as Python repr."""
+        return json.dumps({k: getattr(self, k) for k in ("n", "n_lines", "n_lines_skipped", "n_trials",
+                                                         "n_infrequent_tokens", "hits", "hit_rate", "mrr", "ndcg")})
 
 
 class AssociationRules:
@@ -207,6 +254,80 @@ class AssociationRules:
         (a_off, ante, cons), index, F1, boff, bask, inv = self._prepare_baskets(users)
         top = ops.recommend_topn(a_off, ante, cons, F1, boff, bask, n, index=index)
         return top if inv is None else top[inv]
+
+    def _holdout(self, users: TransactionShard, n: int):
+        """(boff, bask, ranks) of the local lines: the CSR of their baskets (ranks ascending)
+        and the leave-one-out rank of every element (ops.holdout_rank), on the users' device."""
+        if not 1 <= n <= 64:
+            raise ValueError(f"holdout_ranks_shard: n = {n} is outside 1..64")
+        self.rules()
+        dev = users.items.device
+        if users.n_lines == 0:
+            return (torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev),
+                    torch.zeros(0, dtype=torch.int32, device=dev))
+        (a_off, ante, cons), index, F1, boff, bask, inv = self._prepare_baskets(users)
+        ranks = ops.holdout_rank(a_off, ante, cons, F1, boff, bask, n, index=index)
+        if inv is None:
+            return boff, bask, ranks
+        # every line takes the elements of its representative
+        cnt = (boff[1:] - boff[:-1])[inv]
+        loff = torch.zeros(inv.numel() + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(cnt, 0, out=loff[1:])
+        pos = torch.repeat_interleave(boff[inv] - loff[:-1], cnt) + torch.arange(int(loff[-1]), device=dev)
+        return loff, bask[pos].contiguous(), ranks[pos].contiguous()
+
+    def holdout_ranks_shard(self, users: TransactionShard, n: int) -> tuple[torch.Tensor, torch.Tensor]:
+        """Leave-one-out ranks of the local U.dat lines: (boff int64 [lines + 1], ranks int32
+        [nnz]) on the users' device.  Line i's basket (its distinct frequent items, ranks
+        ascending) is elements boff[i] .. boff[i + 1]; an element's rank is the 1-based
+        position of that item in the top-n list of the basket without it, 0 for a miss (and
+        for a one-item basket).  Baskets are de-duplicated and the kernel chosen as in
+        recommend_shard."""
+        boff, _, ranks = self._holdout(users, n)
+        return boff, ranks
+
+    def run_evaluate(self, users: TransactionShard, n: int, rank_lines: bool = False):
+        """(Evaluation on every rank, the per-line rank file on rank 0 or None): with
+        ``rank_lines`` one line per U.dat line, ``token:rank`` for every item of its basket
+        in rank order joined by one space, "0" for an empty basket."""
+        ops.primitives.reset_fallbacks()
+        boff, bask, ranks = self._holdout(users, n)
+        if ops.primitives.FALLBACKS:
+            self.stats["fallbacks"] = list(ops.primitives.FALLBACKS)
+            for f in ops.primitives.FALLBACKS:
+                self.log.metric(phase="fallback", what=f, stage="evaluate")
+        dev = boff.device
+        cnt = boff[1:] - boff[:-1]
+        # a trial is an element of a basket of at least two items; the others rank 0
+        hist = torch.bincount(ranks.to(torch.int64), minlength=n + 1)[1:n + 1]
+        lut = torch.from_numpy(self._rank_lut(users.vocab)).to(dev)
+        n_infreq = int((lut[users.items.to(torch.int64)] < 0).sum()) if users.items.numel() else 0
+        extras = np.asarray(users.extras).astype(np.int64)
+        if extras.size:
+            n_infreq += int((lut.cpu().numpy()[extras] < 0).sum())
+        tail = torch.stack([cnt.new_tensor(users.n_lines), (cnt < 2).sum(), cnt[cnt >= 2].sum(),
+                            cnt.new_tensor(n_infreq)])
+        vec = torch.cat([hist, tail]).to(torch.int64)
+        vec = self.comm.all_reduce_(vec).tolist()
+        ev = Evaluation.from_counts(n, vec[n], vec[n + 1], vec[n + 2], vec[n + 3], vec[:n])
+        if not rank_lines:
+            return ev, None
+        parts = [self.comm.gather_varlen(t) for t in (cnt, bask, ranks)]
+        if parts[0] is None:
+            return ev, None
+        items, out = self.result.items, []
+        for c, b, r in zip(*parts):
+            b, r, o = b.tolist(), r.tolist(), 0
+            for k in c.tolist():
+                out.append(" ".join(f"{items[b[i]]}:{r[i]}" for i in range(o, o + k)) if k else "0")
+                o += k
+        return ev, out
+
+    def evaluate(self, users: TransactionShard, n: int) -> Evaluation:
+        """Leave-one-out evaluation of the top-n recommender on U.dat's own baskets (an
+        extension; docs/PARITY.md): hit rate@1..n, MRR and NDCG over all trials of all ranks'
+        lines, identical on every rank (one all-reduce of the n + 4 integers)."""
+        return self.run_evaluate(users, n)[0]
 
     dedup_baskets = True
 

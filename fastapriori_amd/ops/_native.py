@@ -84,6 +84,7 @@ _HOST_SIGS = {
     "fa_write_rules": (C.c_int, [cp, cp] + [vp] * 12 + [i64, C.c_int]),
     "fa_recommend_cpu": (None, [vp, vp, vp, i64, i32, vp, vp, i64, vp, C.c_int]),
     "fa_recommend_topn_cpu": (None, [vp, vp, vp, i64, i32, vp, vp, i64, i32, vp, C.c_int]),
+    "fa_holdout_rank_cpu": (None, [vp, vp, vp, i64, i32, vp, vp, vp, i64, i32, vp, C.c_int]),
     "fa_condense_cpu": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, vp, C.c_int]),
     "fa_write_freq_itemsets": (C.c_int, [cp, vp, vp, i32, vp, vp, vp, C.c_int, C.c_int, C.c_int]),
     "fa_cpu_histogram": (None, [vp, i64, i64, vp, C.c_int]),
@@ -159,6 +160,8 @@ _HIP_SIGS = {
     "fa_hip_recommend_indexed": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, vp, vp, i64, vp, vp]),
     "fa_hip_recommend_topn": (C.c_int, [vp, vp, vp, i64, i32, vp, vp, i64, i32, vp, vp]),
     "fa_hip_recommend_topn_indexed": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, vp, vp, i64, i32, vp, vp]),
+    "fa_hip_holdout_rank": (C.c_int, [vp, vp, vp, i64, i32, vp, vp, vp, i64, i32, vp, vp]),
+    "fa_hip_holdout_rank_indexed": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, vp, vp, vp, i64, i32, vp, vp]),
     "fa_hip_parse_tiles": (i64, [i64]),
     "fa_hip_tparse_tiles": (i64, [i64, i64]),
     "fa_hip_tline_count": (C.c_int, [vp, i64, i64, vp, vp]),

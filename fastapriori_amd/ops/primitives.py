@@ -1362,6 +1362,44 @@ def recommend_topn(ante_off, ante, cons, F1: int, boff, bask, n: int, index=None
     return out
 
 
+def holdout_rank(ante_off, ante, cons, F1: int, boff, bask, n: int, index=None) -> torch.Tensor:
+    """Leave-one-out rank per element of the basket CSR -> int32 [nnz] (no counterpart in the
+    reference).
+
+    Trial t hides ``bask[t]`` from its basket: the result is the 1-based position of the
+    hidden item in the ``recommend_topn`` list of the basket without it, 0 when it is not
+    among the n entries (a one-item basket's only trial is 0: nothing is left to fire a
+    rule).  So a rule with the hidden item in its antecedent does not fire, one with it as
+    consequent may.  1 <= n <= 64; ``index`` as in ``recommend``."""
+    if not 1 <= n <= 64:
+        raise ValueError(f"holdout_rank: n = {n} is outside 1..64")
+    T = bask.numel()
+    R = cons.numel()
+    dev = bask.device
+    out = torch.zeros(T, dtype=_I32, device=dev)
+    if T == 0 or R == 0:
+        return out
+    M = boff.numel() - 1
+    trow = torch.repeat_interleave(torch.arange(M, dtype=_I64, device=dev), boff[1:] - boff[:-1])
+    if bask.is_cuda:
+        if index is not None:
+            rc = _native.hip().fa_hip_holdout_rank_indexed(_p(index[0]), _p(index[1]), _p(ante_off), _p(ante),
+                                                           _p(cons), R, F1, _p(boff), _p(bask), _p(trow), T, n,
+                                                           _p(out), _stream(bask))
+        else:
+            rc = _native.hip().fa_hip_holdout_rank(_p(ante_off), _p(ante), _p(cons), R, F1, _p(boff), _p(bask),
+                                                   _p(trow), T, n, _p(out), _stream(bask))
+        if rc == 2:  # vocabulary too wide for an LDS bitset: host path
+            note_fallback(f"leave-one-out ranks on the host: F1 = {F1} frequent items exceed the kernel's LDS "
+                          "basket bitset (64 KiB)")
+            return holdout_rank(ante_off.cpu(), ante.cpu(), cons.cpu(), F1, boff.cpu(), bask.cpu(), n).to(dev)
+        _native.check(rc, "fa_hip_holdout_rank")
+        return out
+    _native.host().fa_holdout_rank_cpu(_p(ante_off), _p(ante), _p(cons), R, F1, _p(boff), _p(bask), _p(trow), T, n,
+                                       _p(out), num_threads())
+    return out
+
+
 def rules_build_device(levels: list, counts: list, tie_pos: np.ndarray, dev) -> dict:
     """Association rules on the GPU (csrc/hip/rules.hip; AssociationRules.scala:116-182).
 

@@ -132,6 +132,38 @@ def recommend_window(cfg: JobConfig, comm, log: Logger, result, summary: dict) -
     return recs
 
 
+def evaluate_window(cfg: JobConfig, comm, log: Logger, result, summary: dict) -> None:
+    """--evaluate N / --evaluate-ranks (no counterpart in the reference): after the
+    recommendation window, so neither of the reference's timed windows gets slower.  It reads
+    U.dat itself, as count_window reads D.dat, and builds the rules again without their log
+    lines.  Every rank ranks the trials of its own lines (AssociationRules.run_evaluate); the
+    integers are all-reduced, so every rank holds the same Evaluation; rank 0 writes
+    ``<output>evaluation`` (one JSON line) and, with --evaluate-ranks, ``<output>evaluationRanks``
+    (one line per U.dat line), and the others meet it where it reports how that went."""
+    t0 = time.perf_counter()
+    users = io.read_shard(cfg.input + "U.dat", comm)
+    ar = AssociationRules(result, comm, Logger(comm.rank, enabled=False))
+    ev, lines = ar.run_evaluate(users, cfg.evaluate, rank_lines=cfg.evaluate_ranks)
+    for f in ar.stats.get("fallbacks", ()):
+        log.metric(phase="fallback", what=f, stage="evaluate")
+    err = None
+    if comm.is_root:
+        try:
+            io.write_lines([ev.as_json()], cfg.output + "evaluation", overwrite=cfg.overwrite)
+            if cfg.evaluate_ranks:
+                io.write_lines(lines, cfg.output + "evaluationRanks", overwrite=cfg.overwrite)
+        except (OSError, RuntimeError, ValueError) as e:
+            err = f"{type(e).__name__}: {e}"
+    err = comm.broadcast_object(err)                           # the ranks' meeting point
+    if err:
+        raise RuntimeError(f"--evaluate failed on rank 0: {err}")
+    ms = int((time.perf_counter() - t0) * 1000)
+    log.line(f"Total time for get evaluation {ms}")
+    log.metric(phase="evaluate", n=ev.n, n_lines=ev.n_lines, n_lines_skipped=ev.n_lines_skipped,
+               n_trials=ev.n_trials, n_infrequent_tokens=ev.n_infrequent_tokens, hits=ev.hits, ms=ms)
+    summary.update(evaluate_n=ev.n, n_trials=ev.n_trials, hit_rate_at_n=ev.hit_rate[-1], mrr=ev.mrr)
+
+
 def count_window(cfg: JobConfig, comm, log: Logger, result, summary: dict) -> None:
     """--count-itemsets / --verify-counts (no counterpart in the reference): after the
     mining window and before condense_window, so neither of the reference's timed windows
@@ -306,6 +338,8 @@ def run_job(cfg: JobConfig, comm=None) -> dict:
         recommend_window(cfg, comm, log, result, summary)
         t_rec = int((time.time() - t2) * 1000)
         log.line(f"Total time for get recommends {t_rec}")
+        if cfg.evaluate > 0:
+            evaluate_window(cfg, comm, log, result, summary)
         summary.update(mine_ms=t_mine, recommend_ms=t_rec, n_itemsets=result.n_itemsets,
                        world_size=comm.world_size)
         log.metric(phase="job", **{k: v for k, v in summary.items() if not isinstance(v, dict)})
