@@ -256,6 +256,11 @@ struct DlDesc;   // ../host/fa_dl.h
 FA_API int fa_hip_dl_plan(const fa::DlDesc* desc, int L, long long* ctl, int F1, int32_t* item_map, void* rec,
                           int64_t max_pieces, int32_t* part, int64_t part_cap, int32_t* gpre, int64_t gpre_cap,
                           int sw, hipStream_t st);
+// ... and the regrouping step between the generator and the plan (regroup.hip)
+FA_API int64_t fa_hip_dl_regroup_need(const fa::DlDesc* desc, int L);
+FA_API int fa_hip_dl_regroup(const fa::DlDesc* desc, int L, void* scratch, int64_t bytes, fa::DlDesc* out,
+                             long long* stats, hipStream_t st);
+FA_API int fa_hip_dl_unpermute(const uint32_t* in, const int32_t* perm, int64_t C, uint32_t* out, hipStream_t st);
 FA_API int fa_hip_count_slab_rec_cls(const int64_t* roff, const int32_t* ranks, const int32_t* src, int64_t ncols,
                                      const int32_t* item_map, int F1, int n_used, const int32_t* gpre,
                                      const void* rec, int G, int C, const int32_t* wword, uint32_t* out, int sw,

@@ -18,6 +18,7 @@
 #include "fa_hip.h"
 #include "../host/fa_dl.h"
 #include "../host/fa_limits.h"
+#include "../host/fa_regroup.h"
 #include "../host/fa_slab.h"
 
 namespace fa {
@@ -1066,12 +1067,46 @@ static bool dl_tail(const DlPost* P, const DlDesc* desc, int* L, long long* ch, 
   return false;
 }
 
-static void dl_post(DlPost* P, const DlDesc* desc, int L, long long* ctl, long long* ch, int F1,
-                    double accb_rule, double accb_pack, double lds, hipStream_t st) {
-  P->done = 0;
-  if (ch[kDlStop] && ch[kDlLevels] == 0) return;   // nothing accepted
+// The regrouping step (regroup.hip) of the bundles the post step plans AND counts, set by
+// fastapriori_amd.ops.primitives before each bundle is generated (TUNING.dl_regroup; beside
+// the setters above for the same reason).  It decides the piece records, which ranks that
+// share a bundle's pieces must agree on: every rank sets the same value.
+static int g_regroup = 0;
+FA_API void fa_hip_set_dl_regroup(int on) { g_regroup = on; }
+// Bundles the post step regrouped so far and the levels of the last one (its statistics:
+// the control block's kRgStats slots, fa_regroup.h)
+static int64_t g_regroup_last[2] = {0, 0};
+FA_API void fa_hip_dl_regroup_last(int64_t* out) {
+  for (int i = 0; i < 2; ++i) out[i] = g_regroup_last[i];
+}
+
+// Scratch the regrouped plan and count of these levels take from the workspace (0: the
+// step is off, or the bundle is not eligible): the regrouping's own and the counts in the
+// regrouped numbering.
+static int64_t dl_regroup_ws(const DlDesc* desc, int L) {
+  if (!g_regroup) return 0;
+  const int64_t need = fa_hip_dl_regroup_need(desc, L);
+  if (need == 0) return 0;
+  int64_t C = 0;
+  for (int l = 0; l < L; ++l) C += desc[l].C;
+  return need + ((4 * C + 255) & ~(int64_t)255);
+}
+
+// the chains the post step leaves to the caller
+static bool dl_post_skips(const long long* ch, int L) {
+  if (ch[kDlStop] && ch[kDlLevels] == 0) return true;   // nothing accepted
   // bound error, multi-pass level, end of mining
-  if (ch[kDlOverBound] || ch[kDlMulti] || ch[kDlEnd] || L < 1) return;
+  return ch[kDlOverBound] || ch[kDlMulti] || ch[kDlEnd] || L < 1;
+}
+
+// free_ws / free_bytes: the generator workspace's unused end (the regrouping's scratch).
+// Returns 0, or the scratch bytes a regrouped plan of this bundle needs beyond free_bytes'
+// room (nothing is queued then: the caller grows the workspace and generates again).
+static int64_t dl_post(DlPost* P, const DlDesc* desc, int L, long long* ctl, long long* ch, int F1,
+                    double accb_rule, double accb_pack, double lds, char* free_ws, int64_t free_bytes,
+                    hipStream_t st) {
+  P->done = 0;
+  if (dl_post_skips(ch, L)) return 0;
   int64_t cap = 0;
   int sw = 0, pad = 0, Lp = L;
   const bool packed = accb_pack > 0.0 && dl_tail(P, desc, &L, ch, accb_rule, accb_pack, lds, &Lp, &sw, &cap, &pad);
@@ -1079,7 +1114,7 @@ static void dl_post(DlPost* P, const DlDesc* desc, int L, long long* ctl, long l
   for (int l = 0; l < L; ++l) { C += desc[l].C; R += desc[l].n; }
   const int64_t n_used = ch[kDlNUsed];
   P->C = C;
-  if (C < 1 || C > P->rec_cap || C > P->out_cap || 8 * ((R + 255) / 256) > P->part_cap) return;
+  if (C < 1 || C > P->rec_cap || C > P->out_cap || 8 * ((R + 255) / 256) > P->part_cap) return 0;
   // slab width (fa_slab.h), one accumulator pass
   // (accb_rule: the bytes per accumulator the bundle was accepted with; P->accb, when
   // smaller, the accumulators the count may take where they move the slab up to width 16)
@@ -1088,27 +1123,18 @@ static void dl_post(DlPost* P, const DlDesc* desc, int L, long long* ctl, long l
     accb = accb_pack;
   } else {
     sw = slab_width(n_used, C, P->lds_budget, accb_rule, &cap);
-    if (sw == 0 || C > cap) return;
+    if (sw == 0 || C > cap) return 0;
     if (!P->wword) slab_acc_upgrade(n_used, C, P->lds_budget, P->accb, &sw, &cap, &accb);
   }
   P->accb = accb;                                  // what the count uses (dl_plan_from_post)
-  if (fa_hip_dl_plan(desc, L, ctl, F1, P->item_map, P->rec, C, P->part, P->part_cap, P->gpre, P->gpre_cap,
-                     slab_layout(sw, pad), st) != 0) {
-    // (e.g. long prefixes past gpre_cap: the caller plans -- a packed bundle cut back to the
-    // levels the unpacked rule accepts, which the caller's planner knows)
-    if (packed) dl_tail_cut(desc, &L, Lp, ch);
-    return;
-  }
-  (void)hipMemsetAsync(P->out, 0, 4 * (size_t)C, st);
-  P->sw = slab_layout(sw, pad);
-  P->cap = cap;
-  P->done = 1;
-  // trimming before level k: the rows that keep >= k of the bundle's items
-  P->trim = 0;
+  // trimming before level k: the rows that keep >= k of the bundle's items (decided before
+  // the plan is queued: a bundle the caller trims and counts keeps the generator's groups)
+  int trim = 0;
+  bool caller_decides = false;
   if (!P->trim_ok || P->T <= 0) {
     // no trimming
   } else if (!P->len_hist || P->T < P->trim_min_rows) {
-    if (!P->len_hist && P->T >= P->trim_min_rows) return;   // the caller decides (and counts)
+    caller_decides = !P->len_hist && P->T >= P->trim_min_rows;   // (and the caller counts)
   } else {
     const uint64_t* mk = reinterpret_cast<const uint64_t*>(ch + kDlBits);
     double num = 0.0, den = 0.0;
@@ -1120,22 +1146,57 @@ static void dl_post(DlPost* P, const DlDesc* desc, int L, long long* ctl, long l
       double est_rows = 0.0, est_nnz = 0.0;
       trim_estimate(P->len_hist, kTrimHist, num / den, (int)P->k, &est_rows, &est_nnz);
       const double T = (double)std::max<int64_t>(P->T, 1), nnz = (double)std::max<int64_t>(P->nnz, 1);
-      P->trim = (est_rows < P->trim_rows_frac * T || est_nnz < P->trim_nnz_frac * nnz) ? 1 : 0;
+      trim = (est_rows < P->trim_rows_frac * T || est_nnz < P->trim_nnz_frac * nnz) ? 1 : 0;
     }
   }
-  if (P->trim) return;                                      // the caller trims, then counts
+  // Regrouped (regroup.hip): only what is counted right here, so that the caller never sees
+  // the regrouped numbering -- the counts come back in the generator's order.
+  DlDesc rg[kDlMaxL];
+  const DlDesc* pd = desc;
+  const int32_t* perm = nullptr;
+  uint32_t* cnt_rg = nullptr;
+  const int64_t rg_bytes = (trim || caller_decides) ? 0 : dl_regroup_ws(desc, L);
+  if (rg_bytes > free_bytes) return rg_bytes;
+  if (rg_bytes > 0) {
+    const int64_t cb = (4 * C + 255) & ~(int64_t)255;
+    if (fa_hip_dl_regroup(desc, L, free_ws + cb, free_bytes - cb, rg, ctl + kRgStats, st) == 0) {
+      pd = rg;
+      perm = reinterpret_cast<const int32_t*>(free_ws + cb);
+      cnt_rg = reinterpret_cast<uint32_t*>(free_ws);
+      ++g_regroup_last[0];
+      g_regroup_last[1] = L;
+    }
+  }
+  if (fa_hip_dl_plan(pd, L, ctl, F1, P->item_map, P->rec, C, P->part, P->part_cap, P->gpre, P->gpre_cap,
+                     slab_layout(sw, pad), st) != 0) {
+    // (e.g. long prefixes past gpre_cap: the caller plans -- a packed bundle cut back to the
+    // levels the unpacked rule accepts, which the caller's planner knows)
+    if (packed) dl_tail_cut(desc, &L, Lp, ch);
+    return 0;
+  }
+  (void)hipMemsetAsync(P->out, 0, 4 * (size_t)C, st);
+  if (cnt_rg) (void)hipMemsetAsync(cnt_rg, 0, 4 * (size_t)C, st);
+  P->sw = slab_layout(sw, pad);
+  P->cap = cap;
+  P->done = 1;
+  P->trim = trim;
+  if (caller_decides || trim) return 0;                     // the caller trims, then counts
   const int64_t W = (P->ncols + 63) / 64, nslabs = (W + sw - 1) / sw;
   const bool weighted = P->wword != nullptr;
   const int64_t nacc = slab_acc_count(C, slab_acc_bytes(P->accb, weighted));
   P->n_wg = slab_workgroups(nslabs, (int64_t)P->lds_kernel,
                             slab_kernel_lds_pack(n_used, sw, pad, slab_acc_words(nacc), slab_map_lds(F1)));
   if (fa_hip_count_slab_rec_cls(P->roff, P->ranks, P->src, P->ncols, P->item_map, F1, (int)n_used, P->gpre, P->rec,
-                                0, (int)C, P->wword, P->out, slab_layout(sw, pad), (int)P->n_wg, nullptr, 0, st,
-                                nullptr,
+                                0, (int)C, P->wword, cnt_rg ? cnt_rg : P->out, slab_layout(sw, pad), (int)P->n_wg,
+                                nullptr, 0, st, nullptr,
                                 reinterpret_cast<const int32_t*>(ctl + kDlPiecesI32),
-                                slab_acc_mode(P->accb, weighted)) != 0)
-    return;
+                                slab_acc_mode(P->accb, weighted)) != 0 ||
+      (cnt_rg && fa_hip_dl_unpermute(cnt_rg, perm, C, P->out, st) != 0)) {
+    if (cnt_rg) P->done = 0;                                // (the records are regrouped: the caller plans)
+    return 0;
+  }
   P->done = 2;
+  return 0;
 }
 
 FA_API int fa_hip_dl_more(int F1, void* ws, int64_t ws_bytes, int64_t ws_used, long long* ctl, long long* ctl_host,
@@ -1259,6 +1320,16 @@ FA_API int fa_hip_dl_more(int F1, void* ws, int64_t ws_bytes, int64_t ws_used, l
     d.base = desc[l - 1].base + desc[l - 1].C;
   }
   info[0] = w - w0;
-  if (post) dl_post(static_cast<DlPost*>(post), desc, L, ctl, ctl_host, F1, accb, accb_pack, lds, st);
+  // the regrouping's scratch is the workspace's unused end: too small for a bundle that
+  // regroups (after the tail cut, and not trimmed), and the caller grows the workspace and
+  // generates again, as for the chain's own buffers (every rank alike)
+  if (post) {
+    const int64_t more = dl_post(static_cast<DlPost*>(post), desc, L, ctl, ctl_host, F1, accb, accb_pack, lds, w,
+                                 ws_bytes - (w - w0), st);
+    if (more > 0) {
+      info[0] = 2 * ((w - w0) + more);
+      return 5;
+    }
+  }
   FA_LAUNCH_RET();
 }

@@ -25,6 +25,7 @@
 //   kDlEmpty     the chain stopped on a speculative level with no candidates
 //   kDlPieces    pieces of the device plan (levels.hip k_dl_pieces_scan)
 //   kDlPiecesI32 the same as int32 in the word's low half: the count kernel's g_dev
+//   (224 .. 351  the regrouping step's statistics: fa_regroup.h kRgStats)
 //   kDlBits ..   used-item bitset of level 0, kDlBitsW words (F1 <= kAgMaxF1 bits)
 // The host-loop chain's block is the first kDlGl words (no G_l, no bitset).
 #pragma once

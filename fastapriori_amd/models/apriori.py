@@ -418,6 +418,9 @@ class FastApriori:
         self._dl_tail_accb = 0.0            # bytes per accumulator of a packed tail bundle; 0: rule off
         if TUNING.dl_tail_bundle and unit and Pm.slab_map_lds(F1) > 0 and tail_rows >= TUNING.dl_acc8_min_rows:
             self._dl_tail_accb = 1.0 if int(TUNING.dl_acc8_bundles) else 2.0 if TUNING.dl_acc16_bundles else 4.0
+        # the regrouping step (TUNING.dl_regroup) decides the piece records, which ranks that
+        # divide a bundle's pieces share: the same rank-agreed row count as the tail rule's
+        regroup = bool(TUNING.dl_regroup) and tail_rows >= TUNING.dl_regroup_min_rows
         c_bound = int(lds // accb)
         st = torch.cuda.current_stream(self._dev).cuda_stream
         f2 = self._f2_dev
@@ -467,7 +470,7 @@ class FastApriori:
                     c = Pm.dl_bundle_gen(S, P0, n_src, n_const, n_bound, m0, F1, c_bound, lds, TUNING.bundle_growth,
                                          max_lv, st, post=post, accb=accb,
                                          tail_accb=self._dl_tail_accb if post else 0.0,
-                                         tail_levels=tail_levels if max_lv > 1 else 0)
+                                         tail_levels=tail_levels if max_lv > 1 else 0, regroup=regroup)
                 if c[K.kDlOverBound]:
                     raise RuntimeError(f"device bundle at level {k}: |F_{k - 1}| exceeds its bound {n_bound}")
                 if c[K.kDlEnd]:

@@ -42,6 +42,9 @@ _HOST_SIGS = {
     "fa_cands_export": (None, [vp, vp, vp, vp]),
     "fa_cands_free": (None, [vp]),
     "fa_level_plan": (C.c_int, [vp, vp, i64, vp, vp, i32, vp, vp, i64, vp, i64, vp]),
+    # host model of the device bundles' regrouping step (csrc/host/regroup.cpp)
+    "fa_dl_regroup": (C.c_int, [vp, C.c_int]),
+    "fa_dl_regroup_const": (i64, [C.c_int]),
     # the slab kernel's LDS rule and the trimming estimate (csrc/host/fa_slab.h)
     "fa_slab_width": (C.c_int, [i64, i64, dbl, dbl, I64P]),
     "fa_slab_total_limit": (i64, [i64, dbl, dbl]),
@@ -135,6 +138,12 @@ _HIP_SIGS = {
     "fa_hip_set_lane_deal": (None, [C.c_int]),
     "fa_hip_set_dl_tail": (None, [dbl, C.c_int]),
     "fa_hip_set_piece_part": (C.c_int, [C.c_int, C.c_int]),
+    # the regrouping step of one-pass bundles (regroup.hip) and its switch in the post step
+    "fa_hip_set_dl_regroup": (None, [C.c_int]),
+    "fa_hip_dl_regroup_last": (None, [vp]),
+    "fa_hip_dl_regroup_need": (i64, [vp, C.c_int]),
+    "fa_hip_dl_regroup": (C.c_int, [vp, C.c_int, vp, i64, vp, vp, vp]),
+    "fa_hip_dl_unpermute": (C.c_int, [vp, vp, i64, vp, vp]),
     "fa_hip_dl_gpre_need": (i64, [vp, C.c_int]),
     "fa_hip_dl_plan_window": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, i64, vp, i64, vp, i64, i64, i64, C.c_int,
                                         vp]),

@@ -68,8 +68,8 @@ def _deps(kind: str) -> list[str]:
     # the exported rules' measures, which the kernels share with the host library (included by
     # relative path)
     return hip_sources() + sorted(glob.glob(os.path.join(CSRC, "hip", "*.h"))) + [
-        os.path.join(CSRC, "host", h) for h in ("fa_dl.h", "fa_limits.h", "fa_query.h", "fa_rule_measures.h",
-                                                "fa_slab.h")]
+        os.path.join(CSRC, "host", h) for h in ("fa_dl.h", "fa_limits.h", "fa_query.h", "fa_regroup.h",
+                                                "fa_rule_measures.h", "fa_slab.h")]
 
 
 def source_id(kind: str, flags: list[str] | None = None) -> str:

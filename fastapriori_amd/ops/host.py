@@ -31,6 +31,50 @@ def apriori_gen(prev: np.ndarray):
     return prefix[:G], ext_off, ext[:Cn]
 
 
+class RgLevelC(C.Structure):
+    """regroup.cpp RgLevel: one level of a bundle in the generator's form and its regrouped form."""
+    _fields_ = [(n, C.c_void_p) for n in ("P", "cnt", "off", "ex")] + \
+               [(n, C.c_int64) for n in ("n", "C", "m")] + \
+               [(n, C.c_void_p) for n in ("cnt_out", "off_out", "ex_out", "perm")] + \
+               [(n, C.c_int64) for n in ("pieces_prefix", "pieces_rule", "rounds", "kept_prefix")]
+
+
+def dl_regroup(levels) -> tuple[bool, list[dict]]:
+    """Host model of the device bundles' regrouping step (csrc/host/fa_regroup.h, regroup.cpp).
+
+    levels: per level (P int32 [n, m] parent rows, cnt int32 [n] extensions per row, ex int32 [C]
+    their ids in row order), as the generator leaves them.  Returns (the bundle regroups, per
+    level dict(cnt int32 [n], off int64 [n + 1], ex int32 [C], perm int32 [C] with perm[new
+    index] = old index inside the level, pieces_prefix, pieces_rule, rounds, kept_prefix)).
+    """
+    L = len(levels)
+    arr = (RgLevelC * L)()
+    keep, out = [], []
+    for l, (P, cnt, ex) in enumerate(levels):
+        P = np.ascontiguousarray(P, dtype=np.int32)
+        cnt = np.ascontiguousarray(cnt, dtype=np.int32)
+        ex = np.ascontiguousarray(ex, dtype=np.int32)
+        n, m = P.shape
+        Cn = int(ex.size)
+        assert cnt.shape == (n,) and int(cnt.sum()) == Cn
+        off = np.concatenate([[0], np.cumsum(cnt, dtype=np.int64)]).astype(np.int64)
+        o = dict(cnt=np.zeros(n, np.int32), off=np.zeros(n + 1, np.int64), ex=np.zeros(max(Cn, 1), np.int32),
+                 perm=np.zeros(max(Cn, 1), np.int32))
+        keep.append((P, cnt, ex, off))
+        a = arr[l]
+        a.P, a.cnt, a.off, a.ex = P.ctypes.data, cnt.ctypes.data, off.ctypes.data, ex.ctypes.data
+        a.n, a.C, a.m = n, Cn, m
+        a.cnt_out, a.off_out, a.ex_out, a.perm = (o[k].ctypes.data for k in ("cnt", "off", "ex", "perm"))
+        out.append(o)
+    regrouped = bool(_native.host().fa_dl_regroup(C.addressof(arr), L))
+    for l, o in enumerate(out):
+        Cn = int(arr[l].C)
+        o["ex"], o["perm"] = o["ex"][:Cn], o["perm"][:Cn]
+        for k in ("pieces_prefix", "pieces_rule", "rounds", "kept_prefix"):
+            o[k] = int(getattr(arr[l], k))
+    return regrouped, out
+
+
 @dataclass
 class RuleTable:
     """Rules after the cut, in recommendation order (conf desc, tiebreak)."""

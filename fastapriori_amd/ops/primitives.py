@@ -2129,7 +2129,8 @@ def dl_lds_budget(F1: int) -> int:
 
 def dl_bundle_gen(S: DeviceLevelState, P0: int, n_src: int | None, n_const: int, n_bound: int, m0: int, F1: int,
                   c_bound: int, lds: int, growth: float, max_levels: int, stream: int, post: bool = False,
-                  accb: float = 4.0, tail_accb: float = 0.0, tail_levels: int = 0) -> np.ndarray:
+                  accb: float = 4.0, tail_accb: float = 0.0, tail_levels: int = 0,
+                  regroup: bool | None = None) -> np.ndarray:
     """Candidates of a device bundle: level 0 from F_{k-1} rows P0 and the speculative
     levels 1 .. max_levels-1 (accepted on the device), all queued before ONE
     synchronisation (accb: LDS bytes per slab accumulator, 2 = packed u16 counters).
@@ -2158,6 +2159,8 @@ def dl_bundle_gen(S: DeviceLevelState, P0: int, n_src: int | None, n_const: int,
         S.post.done = 0
         lane_deal(lib, S.rows_hint)    # (the post step's plan)
         lib.fa_hip_set_dl_tail(float(tail_accb) if post else 0.0, int(tail_levels))
+        # (regroup: the caller's rank-agreed decision, FastApriori._mine_device; None: the knob's)
+        lib.fa_hip_set_dl_regroup(int(bool(TUNING.dl_regroup if regroup is None else regroup) and post))
         rc = lib.fa_hip_dl_more(F1, _p(S.ws), S.ws.numel(), int(S.info[0]), _p(S.ctl), _p(S.ctl_h), float(growth),
                                 int(max_levels), float(lds), float(accb), int(c_bound), S.desc.ctypes.data,
                                 info.ctypes.data,
@@ -2183,8 +2186,54 @@ def lane_deal(lib, rows: int) -> None:
     lib.fa_hip_set_lane_deal(int(0 <= TUNING.lane_deal_min_rows <= rows))
 
 
+def dl_regroup(S: DeviceLevelState, L: int, dev) -> dict | None:
+    """The regrouping step on its own (regroup.hip fa_hip_dl_regroup; the miner reaches it inside
+    the post step, gen.hip dl_post): S.desc[:L] regrouped.  Returns None when the bundle is not
+    eligible (a prefix past kDlInline ids), else dict(desc: the regrouped level table for
+    dl_plan(desc=...), perm: int32 [C] with perm[new bundle index] = the generator's, stats:
+    int64 [L, 4] per level (the prefix plan's pieces, the rule's, rounds, 1 = kept the prefix
+    plan), scratch: the buffer desc points into)."""
+    lib = _native.hip()
+    need = int(lib.fa_hip_dl_regroup_need(S.desc.ctypes.data, L))
+    if need == 0:
+        return None
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    stats = torch.zeros((L, 4), dtype=_I64, device=dev)
+    desc = S.desc.copy()
+    st = torch.cuda.current_stream(dev).cuda_stream
+    _native.check(lib.fa_hip_dl_regroup(S.desc.ctypes.data, L, _p(scratch), need, desc.ctypes.data, _p(stats), st),
+                  "fa_hip_dl_regroup")
+    C = int(S.desc["C"][:L].sum())
+    perm = scratch[:4 * C].view(_I32)
+    return dict(desc=desc, perm=perm, stats=stats, scratch=scratch)
+
+
+def dl_regroup_last(S: DeviceLevelState | None = None) -> tuple[int, np.ndarray | None]:
+    """(bundles the post step regrouped so far in this process, the last one's statistics: int64
+    [L, 4] per level as dl_regroup's, read from S's control block (fa_regroup.h kRgStats) --
+    S: the state that generated it, default the first device state; None before the first
+    bundle).  For tests and probes."""
+    last = np.zeros(2, dtype=np.int64)
+    _native.hip().fa_hip_dl_regroup_last(last.ctypes.data)
+    S = S if S is not None else next(iter(_DL_STATE.values()), None)
+    if last[0] == 0 or S is None:
+        return int(last[0]), None
+    at, L = int(_native.host().fa_dl_regroup_const(1)), int(last[1])
+    return int(last[0]), S.ctl[at:at + 4 * L].cpu().numpy().reshape(L, 4)
+
+
+def dl_unpermute(cnt: torch.Tensor, perm: torch.Tensor) -> torch.Tensor:
+    """Counts of a regrouped plan back in the generator's order: out[perm[e]] = cnt[e]
+    (regroup.hip k_dl_unpermute)."""
+    out = torch.empty_like(cnt)
+    st = torch.cuda.current_stream(cnt.device).cuda_stream
+    _native.check(_native.hip().fa_hip_dl_unpermute(_p(cnt), _p(perm), cnt.numel(), _p(out), st),
+                  "fa_hip_dl_unpermute")
+    return out
+
+
 def dl_plan(S: DeviceLevelState, L: int, F1: int, n_used: int, C: int, lds: int, dev, accb: float = 4.0,
-            cnt_accb: float | None = None, pad: int = 0) -> dict:
+            cnt_accb: float | None = None, pad: int = 0, desc=None) -> dict:
     """Device piece plan of a bundle's C candidates (levels.hip fa_hip_dl_plan), queued
     on the stream right after the generator's synchronisation: it depends on the
     candidates only, not on the row layout, so the host's trimming decision runs
@@ -2194,7 +2243,8 @@ def dl_plan(S: DeviceLevelState, L: int, F1: int, n_used: int, C: int, lds: int,
     its own): the slab rows' pad shift, which the lane deal's slot columns and dl_count's launch
     follow.  The width and capacity are the rule's at pad shift 0; a thinner padding only
     shrinks the rows' footprint (slab_rows_bytes falls with pad), so what fits there fits here.
-    Returns the plan for dl_count."""
+    desc: the level table to plan (default S.desc; dl_regroup's regrouped table plans the same
+    candidates in its own numbering).  Returns the plan for dl_count."""
     st = torch.cuda.current_stream(dev).cuda_stream
     sw, cap = slab_width(n_used, C, lds, accb)
     if sw == 0 or C > cap:
@@ -2206,13 +2256,14 @@ def dl_plan(S: DeviceLevelState, L: int, F1: int, n_used: int, C: int, lds: int,
         sw, cap, accb = int(sw_c.value), int(cap_c.value), float(accb_c.value)
     item_map = torch.empty(max(F1, 1), dtype=_I32, device=dev)
     rec = torch.empty(12 * C + 12, dtype=_I32, device=dev)
-    R = int(S.desc["n"][:L].sum())                   # parent rows of the bundle
+    desc = S.desc if desc is None else desc          # (a regrouped table: dl_regroup)
+    R = int(desc["n"][:L].sum())                     # parent rows of the bundle
     part = torch.empty(8 * max(1, (R + 255) // 256), dtype=_I32, device=dev)
     lib = _native.hip()
-    gn = int(lib.fa_hip_dl_gpre_need(S.desc.ctypes.data, L))
+    gn = int(lib.fa_hip_dl_gpre_need(desc.ctypes.data, L))
     gpre = torch.empty(max(gn, 1), dtype=_I32, device=dev)
     lane_deal(lib, S.rows_hint)
-    _native.check(lib.fa_hip_dl_plan(S.desc.ctypes.data, L, _p(S.ctl), F1, _p(item_map), _p(rec), C,
+    _native.check(lib.fa_hip_dl_plan(desc.ctypes.data, L, _p(S.ctl), F1, _p(item_map), _p(rec), C,
                                      _p(part), part.numel(), _p(gpre), gpre.numel(), slab_layout(sw, pad), st),
                   "fa_hip_dl_plan")
     out = torch.zeros(C, dtype=_I32, device=dev)

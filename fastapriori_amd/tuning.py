@@ -74,6 +74,19 @@ class Tuning:
     # bundle and its all-reduce, so it never looks at a rank's own shard.  Every other bundle
     # is cut exactly as without the knob.
     dl_tail_bundle: bool = True
+    # one-pass device bundles the post step plans and counts: every candidate grouped under
+    # its best parent -- any (k-1)-subset that is a parent row -- instead of its lexicographic
+    # prefix (csrc/host/fa_regroup.h, csrc/hip/regroup.hip), the counts put back in the
+    # generator's order before the all-reduce.  Off: the prefix plan, byte for byte.  It
+    # decides the piece records, so every rank sets the same value.
+    dl_regroup: bool = True
+    # ... from this many lines per counting rank (the database's lines / ranks, as the tail
+    # rule's: the same on every rank).  The step's cost is fixed per bundle -- one workgroup
+    # per level, 0.87 ms on T10I4's levels 3-12 -- while the slab time it saves grows with
+    # the rows counted (1.78 ms per 100 M rows there): T10I4D100M 36.65 -> 35.81 ms, but
+    # the 12.5M-row shard 5.80 -> 6.32 ms and T10I4D100K 1.09 -> 1.20 ms without the
+    # threshold, which sits above the ~50 M rows where the two meet
+    dl_regroup_min_rows: int = 1 << 26
     mp_window_items: bool = True        # window-by-window levels: each window's slab holds only its own used items
     # window-by-window levels: a window counts only the rows holding >= k of its own items
     # (its items' bitmap compacted to them, count.hip k_win_compact) when the binomial
