@@ -6,6 +6,7 @@
 // step tests 64 consecutive rules, one per lane, and __ballot + ffs picks the
 // earliest match, so the scan stops at the first 64-rule chunk that hits.
 #include "fa_hip.h"
+#include "../host/fa_combine.h"
 
 namespace fa {
 
@@ -428,6 +429,226 @@ __global__ __launch_bounds__(256) void k_holdout_rank_indexed(
   if (lane == 0) out[t] = at ? __ffsll((long long)at) : 0;
 }
 
+// ---------------------------------------------------------------------------
+// Combined scoring (an extension, --combine sum|votes; docs/PARITY.md): EVERY firing rule
+// of a basket adds its weight w[r] (int64, 1 .. 2^32) to the score S(c) of its consequent,
+// f(c) is the smallest firing rule id of c, and the list is the consequents with S > 0 by
+// S descending, then f ascending (f is distinct per consequent, so the order is strict),
+// cut to n.  There is no early exit, so both kernels are indexed: a basket visits the
+// per-item rule lists of its own items (k_recommend_indexed's), every firing rule once.
+//
+// One wave per basket or trial, persistent over them.  Each wave owns four LDS rows over
+// the F1 items (../host/fa_combine.h: size, order and the waves per workgroup): scores,
+// first rules, the list of touched consequents and the basket bitset.  A firing lane adds
+// its weight with a 64-bit LDS atomic and takes the min of its id; the lane whose add
+// returns 0 appends the consequent to the touched list (weights are >= 1 and the sums stay
+// below 2^63, so exactly one add per consequent returns 0).  Integer adds and mins do not
+// depend on their order: two runs give the same output.  After the walk a consequent's
+// place is 1 + the number of touched consequents that beat it -- no sort.  Only the
+// touched entries and the basket's words are cleared before the next basket.
+//
+// A wave touches its own rows only, so the kernels hold no workgroup barrier (idle waves
+// simply leave): wave_lds_sync orders a wave's LDS accesses.  As above, every loop exit
+// and every lane count comes from a __ballot / readlane / readfirstlane value.
+// ---------------------------------------------------------------------------
+struct CombRows {
+  unsigned long long* score;   // [F1] S(c), 0 = untouched
+  int32_t* first;              // [F1] f(c), INT32_MAX = untouched
+  int32_t* touched;            // [F1] the consequents with S > 0, in no particular order
+  uint32_t* bs;                // basket bitset
+};
+
+__device__ __forceinline__ int64_t uniform_i64(int64_t v) {
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
+  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)v >> 32));
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v, int l) {
+  const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)v, l);
+  const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(v >> 32), l);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+// wave wv's rows, all cleared
+__device__ __forceinline__ CombRows comb_rows(unsigned char* lds, int wv, int32_t F1) {
+  unsigned char* p = lds + (size_t)wv * (size_t)combine_wave_bytes(F1);
+  CombRows w;
+  w.score = (unsigned long long*)p;
+  p += combine_score_bytes(F1);
+  w.first = (int32_t*)p;
+  p += combine_first_bytes(F1);
+  w.touched = (int32_t*)p;
+  p += combine_touched_bytes(F1);
+  w.bs = (uint32_t*)p;
+  const int lane = lane_id();
+  for (int i = lane; i < F1; i += kWave) {
+    w.score[i] = 0ull;
+    w.first[i] = INT32_MAX;
+  }
+  for (int i = lane; i < (F1 + 31) >> 5; i += kWave) w.bs[i] = 0u;
+  wave_lds_sync();
+  return w;
+}
+
+// The walk over the lists of basket elements [s, e) except item h (-1: none), whose bits
+// (without h) are set in w.bs; usz: the basket's size without h.  Returns the number of
+// touched consequents.
+__device__ __forceinline__ int comb_walk(const CombRows& w, const int64_t* __restrict__ list_off,
+                                         const int32_t* __restrict__ list_rule, const int64_t* __restrict__ ante_off,
+                                         const int32_t* __restrict__ ante, const int32_t* __restrict__ cons,
+                                         const int64_t* __restrict__ weight, const int32_t* __restrict__ bask,
+                                         int64_t s, int64_t e, int32_t h, int64_t usz) {
+  const int lane = lane_id();
+  const unsigned long long below = (1ull << lane) - 1;
+  int nt = 0;
+  for (int64_t j = s; j < e; ++j) {
+    const int32_t item = __builtin_amdgcn_readfirstlane(bask[j]);
+    if (item == h) continue;                 // every rule listed there has h in its antecedent
+    const int64_t lo = uniform_i64(list_off[item]), hi = uniform_i64(list_off[item + 1]);
+    for (int64_t base = lo; base < hi; base += kWave) {
+      const int64_t q = base + lane;
+      bool ok = false;
+      int32_t r = -1, c = -1;
+      if (q < hi) {
+        r = list_rule[q];
+        c = cons[r];
+        const int64_t a0 = ante_off[r], a1 = ante_off[r + 1];
+        ok = !((w.bs[c >> 5] >> (c & 31)) & 1u) && (a1 - a0) <= usz;
+        for (int64_t i = a0; ok && i < a1 - 1; ++i) {   // the last item is `item`, in the basket
+          const int32_t a = ante[i];
+          ok = (w.bs[a >> 5] >> (a & 31)) & 1u;
+        }
+      }
+      bool fresh = false;
+      if (ok) {
+        fresh = atomicAdd(&w.score[c], (unsigned long long)weight[r]) == 0ull;
+        atomicMin(&w.first[c], r);
+      }
+      const unsigned long long mask = __ballot(fresh);
+      if (fresh) w.touched[nt + __popcll(mask & below)] = c;
+      nt += __popcll(mask);
+    }
+  }
+  wave_lds_sync();
+  return nt;
+}
+
+// back to the cleared state: the nt touched entries and the words of basket elements [s, e)
+__device__ __forceinline__ void comb_reset(const CombRows& w, int nt, const int32_t* __restrict__ bask, int64_t s,
+                                           int64_t e) {
+  const int lane = lane_id();
+  for (int i = lane; i < nt; i += kWave) {
+    const int32_t c = w.touched[i];
+    w.score[c] = 0ull;
+    w.first[c] = INT32_MAX;
+  }
+  for (int64_t i = s + lane; i < e; i += kWave) w.bs[bask[i] >> 5] = 0u;
+  wave_lds_sync();
+}
+
+// out_rule[u][j] = f of the j-th entry (-1 padded), out_score[u][j] = its S (0 padded).
+// Touched consequent i (lane i of its 64-chunk) counts the touched consequents that beat it,
+// chunk by chunk: a chunk's (S, f) sit in registers, one per lane, and are read by readlane.
+__global__ __launch_bounds__(256) void k_recommend_combined(
+    const int64_t* __restrict__ list_off, const int32_t* __restrict__ list_rule,
+    const int64_t* __restrict__ ante_off, const int32_t* __restrict__ ante, const int32_t* __restrict__ cons,
+    const int64_t* __restrict__ weight, int32_t F1, const int64_t* __restrict__ boff,
+    const int32_t* __restrict__ bask, int64_t M, int32_t n, int32_t* __restrict__ out_rule,
+    int64_t* __restrict__ out_score) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char comb_lds[];
+  const int W = (int)(blockDim.x >> 6);
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = lane_id();
+  if ((int64_t)blockIdx.x * W + wv >= M) return;
+  const CombRows w = comb_rows(comb_lds, wv, F1);
+  for (int64_t u = (int64_t)blockIdx.x * W + wv; u < M; u += (int64_t)gridDim.x * W) {
+    const int64_t s = uniform_i64(boff[u]), e = uniform_i64(boff[u + 1]);
+    for (int64_t i = s + lane; i < e; i += kWave) atomicOr(&w.bs[bask[i] >> 5], 1u << (bask[i] & 31));
+    wave_lds_sync();
+    const int nt = comb_walk(w, list_off, list_rule, ante_off, ante, cons, weight, bask, s, e, -1, e - s);
+    int32_t* orule = out_rule + u * n;
+    int64_t* oscore = out_score + u * n;
+    for (int t0 = 0; t0 < nt; t0 += kWave) {
+      const int i = t0 + lane;
+      unsigned long long S = 0ull;
+      int32_t f = INT32_MAX;
+      if (i < nt) {
+        const int32_t c = w.touched[i];
+        S = w.score[c];
+        f = w.first[c];
+      }
+      int beat = 0;
+      for (int k0 = 0; k0 < nt; k0 += kWave) {
+        const int k = k0 + lane;
+        unsigned long long So = 0ull;
+        int32_t fo = INT32_MAX;
+        if (k < nt) {
+          const int32_t co = w.touched[k];
+          So = w.score[co];
+          fo = w.first[co];
+        }
+        const int m = min(kWave, nt - k0);
+        for (int x = 0; x < m; ++x) {
+          const unsigned long long Sx = readlane_u64(So, x);
+          const int32_t fx = __builtin_amdgcn_readlane(fo, x);
+          beat += (Sx > S || (Sx == S && fx < f)) ? 1 : 0;
+        }
+      }
+      if (i < nt && beat < n) {
+        orule[beat] = f;
+        oscore[beat] = (int64_t)S;
+      }
+    }
+    if (lane >= min(nt, (int)n) && lane < n) {
+      orule[lane] = -1;
+      oscore[lane] = 0;
+    }
+    comb_reset(w, nt, bask, s, e);
+  }
+}
+
+// Trial t is element t of the basket CSR (k_holdout_rank's): the walk runs over row trow[t]
+// without h = bask[t], and out[t] is the place of h among the touched consequents, 0 when
+// S(h) = 0 or the place exceeds n.
+__global__ __launch_bounds__(256) void k_holdout_rank_combined(
+    const int64_t* __restrict__ list_off, const int32_t* __restrict__ list_rule,
+    const int64_t* __restrict__ ante_off, const int32_t* __restrict__ ante, const int32_t* __restrict__ cons,
+    const int64_t* __restrict__ weight, int32_t F1, const int64_t* __restrict__ boff,
+    const int32_t* __restrict__ bask, const int64_t* __restrict__ trow, int64_t T, int32_t n,
+    int32_t* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char comb_lds[];
+  const int W = (int)(blockDim.x >> 6);
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = lane_id();
+  if ((int64_t)blockIdx.x * W + wv >= T) return;
+  const CombRows w = comb_rows(comb_lds, wv, F1);
+  for (int64_t t = (int64_t)blockIdx.x * W + wv; t < T; t += (int64_t)gridDim.x * W) {
+    const int64_t u = uniform_i64(trow[t]);
+    const int32_t h = __builtin_amdgcn_readfirstlane(bask[t]);
+    const int64_t s = uniform_i64(boff[u]), e = uniform_i64(boff[u + 1]);
+    for (int64_t i = s + lane; i < e; i += kWave) {
+      const int32_t b = bask[i];
+      if (b != h) atomicOr(&w.bs[b >> 5], 1u << (b & 31));
+    }
+    wave_lds_sync();
+    const int nt = comb_walk(w, list_off, list_rule, ante_off, ante, cons, weight, bask, s, e, h, e - s - 1);
+    const unsigned long long Sh = w.score[h];
+    const int32_t fh = w.first[h];
+    int beat = 0;
+    for (int k0 = 0; k0 < nt; k0 += kWave) {
+      const int k = k0 + lane;
+      bool b = false;
+      if (k < nt) {
+        const int32_t co = w.touched[k];
+        const unsigned long long So = w.score[co];
+        b = So > Sh || (So == Sh && w.first[co] < fh);
+      }
+      beat += __popcll(__ballot(b));
+    }
+    if (lane == 0) out[t] = (Sh != 0ull && beat < n) ? beat + 1 : 0;
+    comb_reset(w, nt, bask, s, e);
+  }
+}
+
 }  // namespace fa
 
 using namespace fa;
@@ -518,5 +739,57 @@ FA_API int fa_hip_holdout_rank_indexed(const int64_t* list_off, const int32_t* l
   dim3 g((unsigned)((T + kRecWaves - 1) / kRecWaves));
   hipLaunchKernelGGL(k_holdout_rank_indexed, g, dim3(256), lds, st, list_off, list_rule, ante_off, ante, cons, R,
                      F1, boff, bask, trow, T, n, out);
+  FA_LAUNCH_RET();
+}
+
+// The grid of the combined kernels: one wave per unit up to 8 workgroups per CU, past that
+// the persistent waves take several units each.
+static unsigned comb_grid(int64_t units, int W) {
+  static int ncu = 0;
+  if (ncu <= 0) {
+    int dev = 0, v = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
+    ncu = std::max(1, v);
+  }
+  return (unsigned)std::min<int64_t>((units + W - 1) / W, (int64_t)8 * ncu);
+}
+
+// out_rule: int32 [M, n] first rule ids, -1 padded; out_score: int64 [M, n] scores, 0 padded.
+// weight: int64 [R], 1 .. 2^32.  Returns 2 without a launch when one wave's rows do not fit
+// the LDS (fa_combine.h), 3 for R >= 2^31 - 1.
+FA_API int fa_hip_recommend_combined(const int64_t* list_off, const int32_t* list_rule, const int64_t* ante_off,
+                                     const int32_t* ante, const int32_t* cons, const int64_t* weight, int64_t R,
+                                     int32_t F1, const int64_t* boff, const int32_t* bask, int64_t M, int32_t n,
+                                     int32_t* out_rule, int64_t* out_score, hipStream_t st) {
+  if (n < 1 || n > kWave) return (int)hipErrorInvalidValue;
+  if (M <= 0) return 0;
+  if (R >= (int64_t)INT32_MAX) return 3;
+  const int W = combine_waves(F1);
+  if (W == 0) return 2;            // caller falls back to the host path
+  const int lds = (int)std::max<int64_t>(16, W * combine_wave_bytes(F1));
+  const hipError_t err = hipFuncSetAttribute((const void*)k_recommend_combined,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  if (err != hipSuccess) return (int)err;
+  hipLaunchKernelGGL(k_recommend_combined, dim3(comb_grid(M, W)), dim3(64 * W), (size_t)lds, st, list_off, list_rule,
+                     ante_off, ante, cons, weight, F1, boff, bask, M, n, out_rule, out_score);
+  FA_LAUNCH_RET();
+}
+
+// out: int32 [T] places 1..n or 0, one per element of the basket CSR; trow: its row
+FA_API int fa_hip_holdout_rank_combined(const int64_t* list_off, const int32_t* list_rule, const int64_t* ante_off,
+                                        const int32_t* ante, const int32_t* cons, const int64_t* weight, int64_t R,
+                                        int32_t F1, const int64_t* boff, const int32_t* bask, const int64_t* trow,
+                                        int64_t T, int32_t n, int32_t* out, hipStream_t st) {
+  if (n < 1 || n > kWave) return (int)hipErrorInvalidValue;
+  if (T <= 0) return 0;
+  if (R >= (int64_t)INT32_MAX || T >= (int64_t)INT32_MAX) return 3;
+  const int W = combine_waves(F1);
+  if (W == 0) return 2;            // caller falls back to the host path
+  const int lds = (int)std::max<int64_t>(16, W * combine_wave_bytes(F1));
+  const hipError_t err = hipFuncSetAttribute((const void*)k_holdout_rank_combined,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  if (err != hipSuccess) return (int)err;
+  hipLaunchKernelGGL(k_holdout_rank_combined, dim3(comb_grid(T, W)), dim3(64 * W), (size_t)lds, st, list_off,
+                     list_rule, ante_off, ante, cons, weight, F1, boff, bask, trow, T, n, out);
   FA_LAUNCH_RET();
 }

@@ -17,6 +17,7 @@
 #include <chrono>
 #include <unordered_map>
 
+#include "fa_combine.h"
 #include "fa_common.h"
 #include "fa_rule_measures.h"
 
@@ -307,6 +308,131 @@ FA_API void fa_holdout_rank_cpu(const int64_t* ante_off, const int32_t* ante, co
     unset();
   });
 }
+
+// ---------------------------------------------------------------------------
+// Combined scoring on the CPU (an extension, --combine sum|votes; docs/PARITY.md): every
+// firing rule r of a basket (antecedent inside, consequent outside) adds weight[r] (int64,
+// 1 .. 2^32) to the score S of its consequent, f is the consequent's smallest firing rule
+// id, and the list is the consequents with S > 0 by S descending, then f ascending, cut to
+// n.  Sums are exact: R < 2^31 rules of at most 2^32 stay below 2^63.  Device counterpart:
+// csrc/hip/recommend.hip k_recommend_combined / k_holdout_rank_combined.
+// ---------------------------------------------------------------------------
+namespace fa {
+
+// Per-thread state of the walk.  A rule is listed under the last item of its antecedent
+// (built here, by counting), so a basket visits the lists of its own items only.
+struct CombineWalk {
+  const int64_t* ante_off; const int32_t* ante; const int32_t* cons; const int64_t* weight;
+  const std::vector<int64_t>* list_off; const std::vector<int32_t>* list_rule;
+  std::vector<uint64_t> bits;
+  std::vector<int64_t> score;
+  std::vector<int32_t> first, touched;
+
+  CombineWalk(int32_t F1) : bits((size_t)std::max<int64_t>(1, ((int64_t)F1 + 63) / 64), 0),
+                            score((size_t)std::max(F1, 1), 0), first((size_t)std::max(F1, 1), INT32_MAX) {}
+  bool has(int32_t x) const { return (bits[x >> 6] >> (x & 63)) & 1; }
+  // adds up the firing rules of the set in `bits` (usz items), visiting the lists of b[0 .. nb) except h
+  void walk(const int32_t* b, int64_t nb, int32_t h, int64_t usz) {
+    for (int64_t j = 0; j < nb; ++j) {
+      if (b[j] == h) continue;
+      for (int64_t q = (*list_off)[b[j]]; q < (*list_off)[b[j] + 1]; ++q) {
+        const int32_t r = (*list_rule)[q], c = cons[r];
+        const int64_t a0 = ante_off[r], a1 = ante_off[r + 1];
+        if (has(c) || a1 - a0 > usz) continue;
+        bool sub = true;
+        for (int64_t i = a0; i < a1; ++i)
+          if (!has(ante[i])) { sub = false; break; }
+        if (!sub) continue;
+        if (score[c] == 0) touched.push_back(c);
+        score[c] += weight[r];
+        first[c] = std::min(first[c], r);
+      }
+    }
+  }
+  bool beats(int32_t a, int32_t b) const { return score[a] != score[b] ? score[a] > score[b] : first[a] < first[b]; }
+  void reset() {
+    for (int32_t c : touched) { score[c] = 0; first[c] = INT32_MAX; }
+    touched.clear();
+  }
+};
+
+static void combine_lists(const int64_t* ante_off, const int32_t* ante, int64_t R, int32_t F1,
+                          std::vector<int64_t>& list_off, std::vector<int32_t>& list_rule) {
+  list_off.assign((size_t)F1 + 1, 0);
+  list_rule.resize((size_t)R);
+  for (int64_t r = 0; r < R; ++r) ++list_off[(size_t)ante[ante_off[r + 1] - 1] + 1];
+  for (int32_t i = 0; i < F1; ++i) list_off[(size_t)i + 1] += list_off[i];
+  std::vector<int64_t> at(list_off.begin(), list_off.end() - 1);
+  for (int64_t r = 0; r < R; ++r) list_rule[(size_t)at[ante[ante_off[r + 1] - 1]]++] = (int32_t)r;
+}
+
+}  // namespace fa
+
+// out_rule[u * n + j] = f of entry j, -1 past the last one; out_score[u * n + j] = its S, 0
+// there.  1 <= n; R < 2^31.
+FA_API void fa_recommend_combined_cpu(const int64_t* ante_off, const int32_t* ante, const int32_t* cons,
+                                      const int64_t* weight, int64_t R, int32_t F1, const int64_t* bask_off,
+                                      const int32_t* bask, int64_t M, int32_t n, int32_t* out_rule,
+                                      int64_t* out_score, int nthreads) {
+  std::vector<int64_t> list_off;
+  std::vector<int32_t> list_rule;
+  combine_lists(ante_off, ante, R, F1, list_off, list_rule);
+  parallel_for(M, nthreads, 256, [&](int64_t b, int64_t e, int) {
+    CombineWalk w(F1);
+    w.ante_off = ante_off; w.ante = ante; w.cons = cons; w.weight = weight;
+    w.list_off = &list_off; w.list_rule = &list_rule;
+    for (int64_t u = b; u < e; ++u) {
+      const int64_t s = bask_off[u], t = bask_off[u + 1];
+      for (int64_t i = s; i < t; ++i) w.bits[bask[i] >> 6] |= 1ull << (bask[i] & 63);
+      w.walk(bask + s, t - s, -1, t - s);
+      std::sort(w.touched.begin(), w.touched.end(), [&](int32_t x, int32_t y) { return w.beats(x, y); });
+      const int32_t cnt = (int32_t)std::min<size_t>(w.touched.size(), (size_t)n);
+      for (int32_t j = 0; j < n; ++j) {
+        out_rule[u * n + j] = j < cnt ? w.first[w.touched[j]] : -1;
+        out_score[u * n + j] = j < cnt ? w.score[w.touched[j]] : 0;
+      }
+      w.reset();
+      for (int64_t i = s; i < t; ++i) w.bits[bask[i] >> 6] = 0;
+    }
+  });
+}
+
+// Trial t is element t of the basket CSR, trow[t] its row: out[t] = the place of h = bask[t]
+// in the combined list of its basket without h, 0 when S(h) = 0 or the place exceeds n.
+FA_API void fa_holdout_rank_combined_cpu(const int64_t* ante_off, const int32_t* ante, const int32_t* cons,
+                                         const int64_t* weight, int64_t R, int32_t F1, const int64_t* bask_off,
+                                         const int32_t* bask, const int64_t* trow, int64_t T, int32_t n,
+                                         int32_t* out, int nthreads) {
+  std::vector<int64_t> list_off;
+  std::vector<int32_t> list_rule;
+  combine_lists(ante_off, ante, R, F1, list_off, list_rule);
+  parallel_for(T, nthreads, 256, [&](int64_t b, int64_t e, int) {
+    CombineWalk w(F1);
+    w.ante_off = ante_off; w.ante = ante; w.cons = cons; w.weight = weight;
+    w.list_off = &list_off; w.list_rule = &list_rule;
+    for (int64_t t = b; t < e; ++t) {
+      const int64_t u = trow[t], s = bask_off[u], z = bask_off[u + 1];
+      const int32_t h = bask[t];
+      for (int64_t i = s; i < z; ++i)
+        if (bask[i] != h) w.bits[bask[i] >> 6] |= 1ull << (bask[i] & 63);
+      w.walk(bask + s, z - s, h, z - s - 1);
+      int32_t place = 0;
+      if (w.score[h] > 0) {
+        place = 1;
+        for (int32_t c : w.touched) place += w.beats(c, h);
+      }
+      out[t] = place <= n ? place : 0;
+      w.reset();
+      for (int64_t i = s; i < z; ++i) w.bits[bask[i] >> 6] = 0;
+    }
+  });
+}
+
+// fa_combine.h's LDS rule by name: one wave's bytes, the waves per workgroup (0: no wave
+// fits, the launchers return 2) and the LDS limit
+FA_API int64_t fa_combine_wave_bytes(int64_t F1) { return combine_wave_bytes(F1); }
+FA_API int fa_combine_waves(int64_t F1) { return combine_waves(F1); }
+FA_API int64_t fa_combine_lds_max() { return kCombLdsMax; }
 
 // ---------------------------------------------------------------------------
 // Rule export (AssociationRules.all_rules; no counterpart in the reference): every rule

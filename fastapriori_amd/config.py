@@ -96,6 +96,7 @@ class JobConfig:
     verify_counts: bool = False                 # recount every mined itemset of >= 2 items over D.dat and compare
     evaluate: int = 0                           # > 0: also write <out>evaluation (leave-one-out metrics of the top-N lists)
     evaluate_ranks: bool = False                # ... and <out>evaluationRanks (token:rank per U.dat line)
+    combine: str = "first"                      # first | sum | votes: how --top-n and --evaluate build a list
     extra: dict = field(default_factory=dict)
 
 
@@ -171,6 +172,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--evaluate-ranks", action="store_true",
                    help="with --evaluate: also write <output>evaluationRanks/: per U.dat line token:rank for every "
                         "frequent item of the line (0 = not in the list), or 0 when the line has none")
+    p.add_argument("--combine", choices=["first", "sum", "votes"], default="first",
+                   help="with --top-n / --evaluate: how a list is built. first: an item stands where its best firing "
+                        "rule does. sum: every firing rule adds its confidence to its consequent, votes: it adds 1; the "
+                        "items are listed by their sums, ties by their best rule. recommends/ is not affected")
     return p
 
 
@@ -204,6 +209,8 @@ def parse_args(argv=None) -> JobConfig:
     for flag, on in (("--evaluate", a.evaluate), ("--evaluate-ranks", a.evaluate_ranks)):
         if on and a.count_only:
             p.error(f"{flag} cannot be combined with --count-only (nothing is mined)")
+    if a.combine != "first" and not (a.top_n or a.evaluate):
+        p.error(f"--combine {a.combine} requires --top-n or --evaluate")
     if a.verify_counts and a.count_only:
         p.error("--verify-counts cannot be combined with --count-only (nothing is mined)")
     warn_unread_env()
@@ -216,4 +223,4 @@ def parse_args(argv=None) -> JobConfig:
                      min_confidence=0.0 if a.min_confidence is None else a.min_confidence, min_lift=a.min_lift,
                      rules_sort=a.rules_sort or "confidence", rules_limit=a.rules_limit,
                      count_itemsets=a.count_itemsets, count_only=a.count_only, verify_counts=a.verify_counts,
-                     evaluate=a.evaluate, evaluate_ranks=a.evaluate_ranks)
+                     evaluate=a.evaluate, evaluate_ranks=a.evaluate_ranks, combine=a.combine)

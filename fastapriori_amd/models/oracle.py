@@ -232,6 +232,62 @@ def holdout_ranks(res: OracleResult, user_lines: list[list[str]], n: int) -> lis
     return out
 
 
+def _combined_scores(rules, weights, u: frozenset) -> list[tuple[int, int, int]]:
+    """(consequent, S, f) of basket u in list order: S the summed weights of every firing rule
+    with that consequent (Python ints), f the smallest such rule id; S descending, f ascending."""
+    S: dict[int, int] = {}
+    f: dict[int, int] = {}
+    if not u:
+        return []
+    for i, r in [(i, t[1]) for i, t in enumerate(rules) if t[1] not in u and t[0] <= u]:
+        S[r] = S.get(r, 0) + weights[i]
+        f.setdefault(r, i)
+    return sorted(((c, S[c], f[c]) for c in S), key=lambda t: (-t[1], t[2]))
+
+
+def _combine_weights(rules, mode: str) -> list[int]:
+    if mode == "sum":
+        return [int(conf * 4294967296.0) for _, _, conf in rules]      # the product is exact; int() floors it
+    if mode == "votes":
+        return [1] * len(rules)
+    raise ValueError(f"mode {mode!r} is not 'sum' or 'votes'")
+
+
+def recommend_combined(res: OracleResult, user_lines: list[list[str]], n: int, mode: str) -> list[list[tuple[str, int]]]:
+    """Combined scoring per line (an extension: the reference lets one rule decide): every
+    firing rule adds its weight -- floor(conf * 2^32) for ``sum``, 1 for ``votes`` -- to its
+    consequent; the first n consequents by sum descending, then by their first firing rule in
+    sorted order, as (token, sum)."""
+    rules = sort_rules(gen_rules(res), res.items)
+    weights = _combine_weights(rules, mode)
+    rank = {t: i for i, t in enumerate(res.items)}
+    out = []
+    for toks in user_lines:
+        u = frozenset(rank[t] for t in toks if t in rank)
+        out.append([(res.items[c], s) for c, s, _ in _combined_scores(rules, weights, u)[:n]])
+    return out
+
+
+def holdout_ranks_combined(res: OracleResult, user_lines: list[list[str]], n: int,
+                           mode: str) -> list[list[tuple[str, int]]]:
+    """Leave-one-out places per line under combined scoring: for every item h of the line's
+    basket, in rank order, (token, the 1-based place of h in the combined list of the basket
+    without h, or 0 when it is not among its first n).  A basket of fewer than two items has
+    no trial: its item, if any, gets 0."""
+    rules = sort_rules(gen_rules(res), res.items)
+    weights = _combine_weights(rules, mode)
+    rank = {t: i for i, t in enumerate(res.items)}
+    out = []
+    for toks in user_lines:
+        u = frozenset(rank[t] for t in toks if t in rank)
+        line = []
+        for h in sorted(u):
+            order = [c for c, _, _ in _combined_scores(rules, weights, u - {h})[:n]]
+            line.append((res.items[h], order.index(h) + 1 if h in order else 0))
+        out.append(line)
+    return out
+
+
 def count_itemsets(lines: list[list[str]], queries: list[list[str]]) -> list[int]:
     """Support of given itemsets by brute force (an extension: the reference counts only
     what it mines): per query the number of lines that contain every one of its tokens.  A

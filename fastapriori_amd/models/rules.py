@@ -21,6 +21,9 @@ Reference: AssociationRules.scala (class AssociationRules, :17-190).
                                                      HIP k_recommend_topn / k_recommend_topn_indexed
   (none: nothing is evaluated)                       leave-one-out hit rate / MRR / NDCG (evaluate):
                                                      HIP k_holdout_rank / k_holdout_rank_indexed
+  (none: one rule decides)                           combine="sum" | "votes": every firing rule adds
+                                                     its weight to its consequent, lists by the sums:
+                                                     HIP k_recommend_combined / k_holdout_rank_combined
 
 Divergences (documented): when there are no rules at all the reference throws
 on ``rules.keys.min`` (:147); we recommend "0" for every user.  Non-integer
@@ -50,7 +53,8 @@ class Evaluation:
     the definitions are in docs/PARITY.md).  A trial hides one item of a basket of at least
     two items and ranks it in the top-n list of the rest; ``hits[r - 1]`` counts the trials of
     rank r.  The integers are summed over all ranks first, so the floats do not depend on the
-    world size: sums over r ascending in float64, one division by ``n_trials`` at the end."""
+    world size: sums over r ascending in float64, one division by ``n_trials`` at the end.
+    ``combine``: how the lists were built (first | sum | votes)."""
     n: int
     n_lines: int
     n_lines_skipped: int           # lines with fewer than two frequent items: no trial
@@ -60,10 +64,11 @@ class Evaluation:
     hit_rate: list[float]          # hit_rate[k - 1]: trials of rank 1..k over all trials
     mrr: float
     ndcg: float
+    combine: str = "first"
 
     @classmethod
     def from_counts(cls, n: int, n_lines: int, n_lines_skipped: int, n_trials: int, n_infrequent_tokens: int,
-                    hits: list[int]) -> "Evaluation":
+                    hits: list[int], combine: str = "first") -> "Evaluation":
         hits = [int(h) for h in hits]
         assert len(hits) == n
         cum, rr, dcg, acc = [], 0.0, 0.0, 0
@@ -77,12 +82,15 @@ class Evaluation:
             rate, rr, dcg = [0.0] * n, 0.0, 0.0
         else:
             rate, rr, dcg = [c / T for c in cum], rr / T, dcg / T
-        return cls(int(n), int(n_lines), int(n_lines_skipped), T, int(n_infrequent_tokens), hits, rate, rr, dcg)
+        return cls(int(n), int(n_lines), int(n_lines_skipped), T, int(n_infrequent_tokens), hits, rate, rr, dcg,
+                   combine)
 
     def as_json(self) -> str:
-        """One JSON object, keys in field order, floats as Python repr."""
-        return json.dumps({k: getattr(self, k) for k in ("n", "n_lines", "n_lines_skipped", "n_trials",
-                                                         "n_infrequent_tokens", "hits", "hit_rate", "mrr", "ndcg")})
+        """One JSON object, keys in field order, floats as Python repr; ``combine`` follows
+        ``n`` and is written only when it is not ``first``."""
+        keys = ("n",) + (("combine",) if self.combine != "first" else ()) + (
+            "n_lines", "n_lines_skipped", "n_trials", "n_infrequent_tokens", "hits", "hit_rate", "mrr", "ndcg")
+        return json.dumps({k: getattr(self, k) for k in keys})
 
 
 class AssociationRules:
@@ -255,18 +263,58 @@ class AssociationRules:
         top = ops.recommend_topn(a_off, ante, cons, F1, boff, bask, n, index=index)
         return top if inv is None else top[inv]
 
-    def _holdout(self, users: TransactionShard, n: int):
+    def _combine_args(self, combine: str, dev, index, a_off, ante, F1):
+        """(weights on ``dev``, per-item rule lists) for ops.*_combined: the weights come from
+        ops.combine_weights, once per mode, and a device always gets the lists (the combined
+        kernels have no scan form)."""
+        if not hasattr(self, "_weights"):
+            self._weights = {}
+        if (combine, dev) not in self._weights:
+            self._weights[(combine, dev)] = ops.combine_weights(self.rules().conf, combine).to(dev)
+        if index is None and dev.type == "cuda" and self.rules().n_rules:
+            if len(self._rules_dev) == 4:
+                self._rules_dev = self._rules_dev + (ops.primitives.recommend_index(a_off, ante, F1),)
+            index = self._rules_dev[4]
+        return self._weights[(combine, dev)], index
+
+    def recommend_combined_shard(self, users: TransactionShard, n: int, combine: str):
+        """Combined scoring per local U.dat line (``combine``: sum | votes; docs/PARITY.md):
+        (rule int32 [n_lines, n], score int64 [n_lines, n]) on the users' device, see
+        ops.recommend_combined.  An entry's item is ``rules().cons[rule]``, its score the sum of
+        the weights of every firing rule with that consequent.  Baskets are de-duplicated as in
+        recommend_shard."""
+        if not 1 <= n <= 64:
+            raise ValueError(f"recommend_combined_shard: n = {n} is outside 1..64")
+        if combine not in ("sum", "votes"):
+            raise ValueError(f"recommend_combined_shard: combine = {combine!r} is not 'sum' or 'votes'")
+        self.rules()
+        dev = users.items.device
+        if users.n_lines == 0:
+            return torch.zeros((0, n), dtype=torch.int32, device=dev), torch.zeros((0, n), dtype=torch.int64, device=dev)
+        (a_off, ante, cons), index, F1, boff, bask, inv = self._prepare_baskets(users)
+        weight, index = self._combine_args(combine, dev, index, a_off, ante, F1)
+        rule, score = ops.recommend_combined(a_off, ante, cons, weight, F1, boff, bask, n, index=index)
+        return (rule, score) if inv is None else (rule[inv], score[inv])
+
+    def _holdout(self, users: TransactionShard, n: int, combine: str = "first"):
         """(boff, bask, ranks) of the local lines: the CSR of their baskets (ranks ascending)
-        and the leave-one-out rank of every element (ops.holdout_rank), on the users' device."""
+        and the leave-one-out rank of every element (ops.holdout_rank, or with ``combine``
+        sum | votes ops.holdout_rank_combined), on the users' device."""
         if not 1 <= n <= 64:
             raise ValueError(f"holdout_ranks_shard: n = {n} is outside 1..64")
+        if combine not in ops.primitives.COMBINE_MODES:
+            raise ValueError(f"holdout_ranks_shard: combine = {combine!r} is not one of first, sum, votes")
         self.rules()
         dev = users.items.device
         if users.n_lines == 0:
             return (torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev),
                     torch.zeros(0, dtype=torch.int32, device=dev))
         (a_off, ante, cons), index, F1, boff, bask, inv = self._prepare_baskets(users)
-        ranks = ops.holdout_rank(a_off, ante, cons, F1, boff, bask, n, index=index)
+        if combine == "first":
+            ranks = ops.holdout_rank(a_off, ante, cons, F1, boff, bask, n, index=index)
+        else:
+            weight, index = self._combine_args(combine, dev, index, a_off, ante, F1)
+            ranks = ops.holdout_rank_combined(a_off, ante, cons, weight, F1, boff, bask, n, index=index)
         if inv is None:
             return boff, bask, ranks
         # every line takes the elements of its representative
@@ -276,22 +324,25 @@ class AssociationRules:
         pos = torch.repeat_interleave(boff[inv] - loff[:-1], cnt) + torch.arange(int(loff[-1]), device=dev)
         return loff, bask[pos].contiguous(), ranks[pos].contiguous()
 
-    def holdout_ranks_shard(self, users: TransactionShard, n: int) -> tuple[torch.Tensor, torch.Tensor]:
+    def holdout_ranks_shard(self, users: TransactionShard, n: int,
+                            combine: str = "first") -> tuple[torch.Tensor, torch.Tensor]:
         """Leave-one-out ranks of the local U.dat lines: (boff int64 [lines + 1], ranks int32
         [nnz]) on the users' device.  Line i's basket (its distinct frequent items, ranks
         ascending) is elements boff[i] .. boff[i + 1]; an element's rank is the 1-based
         position of that item in the top-n list of the basket without it, 0 for a miss (and
-        for a one-item basket).  Baskets are de-duplicated and the kernel chosen as in
-        recommend_shard."""
-        boff, _, ranks = self._holdout(users, n)
+        for a one-item basket).  ``combine`` sum | votes ranks it in the combined list
+        (recommend_combined_shard) instead.  Baskets are de-duplicated and the kernel chosen as
+        in recommend_shard."""
+        boff, _, ranks = self._holdout(users, n, combine)
         return boff, ranks
 
-    def run_evaluate(self, users: TransactionShard, n: int, rank_lines: bool = False):
+    def run_evaluate(self, users: TransactionShard, n: int, rank_lines: bool = False, combine: str = "first"):
         """(Evaluation on every rank, the per-line rank file on rank 0 or None): with
         ``rank_lines`` one line per U.dat line, ``token:rank`` for every item of its basket
-        in rank order joined by one space, "0" for an empty basket."""
+        in rank order joined by one space, "0" for an empty basket.  ``combine``: the lists the
+        hidden items are ranked in (first | sum | votes)."""
         ops.primitives.reset_fallbacks()
-        boff, bask, ranks = self._holdout(users, n)
+        boff, bask, ranks = self._holdout(users, n, combine)
         if ops.primitives.FALLBACKS:
             self.stats["fallbacks"] = list(ops.primitives.FALLBACKS)
             for f in ops.primitives.FALLBACKS:
@@ -309,7 +360,7 @@ class AssociationRules:
                             cnt.new_tensor(n_infreq)])
         vec = torch.cat([hist, tail]).to(torch.int64)
         vec = self.comm.all_reduce_(vec).tolist()
-        ev = Evaluation.from_counts(n, vec[n], vec[n + 1], vec[n + 2], vec[n + 3], vec[:n])
+        ev = Evaluation.from_counts(n, vec[n], vec[n + 1], vec[n + 2], vec[n + 3], vec[:n], combine)
         if not rank_lines:
             return ev, None
         parts = [self.comm.gather_varlen(t) for t in (cnt, bask, ranks)]
@@ -323,11 +374,12 @@ class AssociationRules:
                 o += k
         return ev, out
 
-    def evaluate(self, users: TransactionShard, n: int) -> Evaluation:
+    def evaluate(self, users: TransactionShard, n: int, combine: str = "first") -> Evaluation:
         """Leave-one-out evaluation of the top-n recommender on U.dat's own baskets (an
         extension; docs/PARITY.md): hit rate@1..n, MRR and NDCG over all trials of all ranks'
-        lines, identical on every rank (one all-reduce of the n + 4 integers)."""
-        return self.run_evaluate(users, n)[0]
+        lines, identical on every rank (one all-reduce of the n + 4 integers).  ``combine``
+        sum | votes evaluates the combined lists."""
+        return self.run_evaluate(users, n, combine=combine)[0]
 
     dedup_baskets = True
 
@@ -379,11 +431,20 @@ class AssociationRules:
             out.extend("0" if v < 0 else items[v] for v in p.tolist())
         return out
 
-    def run_topn(self, users: TransactionShard, n: int, scores: bool = False) -> list[str] | None:
+    def run_topn(self, users: TransactionShard, n: int, scores: bool = False,
+                 combine: str = "first") -> list[str] | None:
         """Ranked top-n for every U.dat line, in file order, on rank 0 (None elsewhere): the
         items' tokens in list order joined by one space, "0" for an empty list.  With
         ``scores`` every entry is ``token:conf``, conf the repr() of the rule's float64
-        confidence (the score is what follows the last ':')."""
+        confidence (the score is what follows the last ':').
+
+        ``combine`` sum | votes: the combined lists (recommend_combined_shard) instead; with
+        ``scores`` an entry is ``token:repr(S / 2**32)`` for sum (the summed confidences; the
+        division of Python ints is correctly rounded) and ``token:S`` (an integer) for votes."""
+        if combine not in ops.primitives.COMBINE_MODES:
+            raise ValueError(f"run_topn: combine = {combine!r} is not one of first, sum, votes")
+        if combine != "first":
+            return self._run_topn_combined(users, n, scores, combine)
         ops.primitives.reset_fallbacks()
         top = self.recommend_topn_shard(users, n)
         if ops.primitives.FALLBACKS:
@@ -402,5 +463,30 @@ class AssociationRules:
                     ent = [f"{items[cons[i]]}:{conf[i]!r}" for i in ids if i >= 0]
                 else:
                     ent = [items[cons[i]] for i in ids if i >= 0]
+                out.append(" ".join(ent) if ent else "0")
+        return out
+
+    def _run_topn_combined(self, users: TransactionShard, n: int, scores: bool, combine: str) -> list[str] | None:
+        ops.primitives.reset_fallbacks()
+        rule, score = self.recommend_combined_shard(users, n, combine)
+        if ops.primitives.FALLBACKS:
+            self.stats["fallbacks"] = list(ops.primitives.FALLBACKS)
+            for f in ops.primitives.FALLBACKS:
+                self.log.metric(phase="fallback", what=f, stage="rules")
+        # both gathers run on every rank; the scores travel as int64
+        rparts = self.comm.gather_varlen(rule.reshape(-1))
+        sparts = self.comm.gather_varlen(score.reshape(-1))
+        if rparts is None:
+            return None
+        items, cons = self.result.items, self.rules().cons.tolist()
+        out = []
+        for rp, sp in zip(rparts, sparts):
+            for ids, sc in zip(rp.reshape(-1, n).tolist(), sp.reshape(-1, n).tolist()):
+                if not scores:
+                    ent = [items[cons[i]] for i in ids if i >= 0]
+                elif combine == "sum":
+                    ent = [f"{items[cons[i]]}:{v / 2 ** 32!r}" for i, v in zip(ids, sc) if i >= 0]
+                else:
+                    ent = [f"{items[cons[i]]}:{v}" for i, v in zip(ids, sc) if i >= 0]
                 out.append(" ".join(ent) if ent else "0")
         return out

@@ -88,6 +88,12 @@ _HOST_SIGS = {
     "fa_recommend_cpu": (None, [vp, vp, vp, i64, i32, vp, vp, i64, vp, C.c_int]),
     "fa_recommend_topn_cpu": (None, [vp, vp, vp, i64, i32, vp, vp, i64, i32, vp, C.c_int]),
     "fa_holdout_rank_cpu": (None, [vp, vp, vp, i64, i32, vp, vp, vp, i64, i32, vp, C.c_int]),
+    # combined scoring (rules.cpp) and its kernels' LDS rule by name (csrc/host/fa_combine.h)
+    "fa_recommend_combined_cpu": (None, [vp, vp, vp, vp, i64, i32, vp, vp, i64, i32, vp, vp, C.c_int]),
+    "fa_holdout_rank_combined_cpu": (None, [vp, vp, vp, vp, i64, i32, vp, vp, vp, i64, i32, vp, C.c_int]),
+    "fa_combine_wave_bytes": (i64, [i64]),
+    "fa_combine_waves": (C.c_int, [i64]),
+    "fa_combine_lds_max": (i64, []),
     "fa_condense_cpu": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, vp, C.c_int]),
     "fa_write_freq_itemsets": (C.c_int, [cp, vp, vp, i32, vp, vp, vp, C.c_int, C.c_int, C.c_int]),
     "fa_cpu_histogram": (None, [vp, i64, i64, vp, C.c_int]),
@@ -171,6 +177,8 @@ _HIP_SIGS = {
     "fa_hip_recommend_topn_indexed": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, vp, vp, i64, i32, vp, vp]),
     "fa_hip_holdout_rank": (C.c_int, [vp, vp, vp, i64, i32, vp, vp, vp, i64, i32, vp, vp]),
     "fa_hip_holdout_rank_indexed": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, vp, vp, vp, i64, i32, vp, vp]),
+    "fa_hip_recommend_combined": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i32, vp, vp, i64, i32, vp, vp, vp]),
+    "fa_hip_holdout_rank_combined": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i32, vp, vp, vp, i64, i32, vp, vp]),
     "fa_hip_parse_tiles": (i64, [i64]),
     "fa_hip_tparse_tiles": (i64, [i64, i64]),
     "fa_hip_tline_count": (C.c_int, [vp, i64, i64, vp, vp]),

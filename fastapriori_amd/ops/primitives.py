@@ -1400,6 +1400,117 @@ def holdout_rank(ante_off, ante, cons, F1: int, boff, bask, n: int, index=None) 
     return out
 
 
+COMBINE_MODES = ("first", "sum", "votes")
+
+
+def combine_weights(conf, mode: str) -> torch.Tensor:
+    """The rules' integer weights for combined scoring -> int64 [R] on the CPU, 1 .. 2^32.
+    ``sum``: floor(conf * 2^32) -- the product with a power of two is exact in float64, and
+    confidence 1.0 gives 2^32; ``votes``: 1.  The one place the weights are computed, for the
+    kernels and the C++ path alike."""
+    conf = np.ascontiguousarray(np.asarray(conf, dtype=np.float64))
+    if mode == "sum":
+        w = np.floor(conf * 4294967296.0).astype(np.int64)
+    elif mode == "votes":
+        w = np.ones(conf.shape, dtype=np.int64)
+    else:
+        raise ValueError(f"combine_weights: mode {mode!r} is not 'sum' or 'votes'")
+    if w.size and (int(w.min()) < 1 or int(w.max()) > 1 << 32):
+        raise ValueError("combine_weights: a weight is outside 1 .. 2^32 (confidences must lie in [2^-32, 1])")
+    return torch.from_numpy(w)
+
+
+def combine_wave_bytes(F1: int) -> int:
+    """fa_combine.h's LDS footprint of one wave of the combined-scoring kernels."""
+    return int(_native.host().fa_combine_wave_bytes(int(F1)))
+
+
+def combine_waves(F1: int) -> int:
+    """Waves per workgroup of the combined-scoring kernels (4, 2 or 1); 0: one wave's rows
+    exceed the LDS and the host path runs."""
+    return int(_native.host().fa_combine_waves(int(F1)))
+
+
+def _combine_fallback(what: str, F1: int) -> None:
+    note_fallback(f"{what} on the host: the score rows of F1 = {F1} frequent items exceed the kernel's LDS "
+                  f"({int(_native.host().fa_combine_lds_max()) >> 10} KiB)")
+
+
+def recommend_combined(ante_off, ante, cons, weight, F1: int, boff, bask, n: int, index=None):
+    """Combined scoring per basket -> (rule int32 [M, n], score int64 [M, n]) (no counterpart
+    in the reference; docs/PARITY.md).
+
+    EVERY firing rule r of a basket (antecedent inside, consequent outside) adds ``weight[r]``
+    (int64, 1 .. 2^32, see combine_weights) to the score S of its consequent; f is the
+    consequent's smallest firing rule id.  The list is the consequents with S > 0 by S
+    descending, then f ascending, cut to n: ``rule`` holds f per entry (-1 padded, the item is
+    ``cons[f]``), ``score`` holds S (0 padded).  1 <= n <= 64.  The kernel is always indexed:
+    ``index`` as in ``recommend``, built here when it is None."""
+    if not 1 <= n <= 64:
+        raise ValueError(f"recommend_combined: n = {n} is outside 1..64")
+    M = boff.numel() - 1
+    R = cons.numel()
+    dev = bask.device
+    rule = torch.full((max(M, 0), n), -1, dtype=_I32, device=dev)
+    score = torch.zeros((max(M, 0), n), dtype=_I64, device=dev)
+    if M <= 0 or R == 0:
+        return rule, score
+    weight = weight.to(dev)
+    if bask.is_cuda:
+        if index is None:
+            index = recommend_index(ante_off, ante, F1)
+        rc = _native.hip().fa_hip_recommend_combined(_p(index[0]), _p(index[1]), _p(ante_off), _p(ante), _p(cons),
+                                                     _p(weight), R, F1, _p(boff), _p(bask), M, n, _p(rule),
+                                                     _p(score), _stream(bask))
+        if rc == 2:  # the rows of one wave do not fit the LDS: host path
+            _combine_fallback("combined scoring", F1)
+            rule, score = recommend_combined(ante_off.cpu(), ante.cpu(), cons.cpu(), weight.cpu(), F1, boff.cpu(),
+                                             bask.cpu(), n)
+            return rule.to(dev), score.to(dev)
+        _native.check(rc, "fa_hip_recommend_combined")
+        return rule, score
+    _native.host().fa_recommend_combined_cpu(_p(ante_off), _p(ante), _p(cons), _p(weight), R, F1, _p(boff),
+                                             _p(bask), M, n, _p(rule), _p(score), num_threads())
+    return rule, score
+
+
+def holdout_rank_combined(ante_off, ante, cons, weight, F1: int, boff, bask, n: int, index=None) -> torch.Tensor:
+    """Leave-one-out place per element of the basket CSR under combined scoring -> int32 [nnz]
+    (no counterpart in the reference).
+
+    Trial t hides ``bask[t]`` from its basket: the result is the 1-based place of the hidden
+    item in the ``recommend_combined`` list of the basket without it, 0 when no firing rule
+    has it as consequent, when the place exceeds n, or for a one-item basket.  A rule with the
+    hidden item in its antecedent does not fire, one with it as consequent may.
+    1 <= n <= 64; ``index`` as in ``recommend_combined``."""
+    if not 1 <= n <= 64:
+        raise ValueError(f"holdout_rank_combined: n = {n} is outside 1..64")
+    T = bask.numel()
+    R = cons.numel()
+    dev = bask.device
+    out = torch.zeros(T, dtype=_I32, device=dev)
+    if T == 0 or R == 0:
+        return out
+    M = boff.numel() - 1
+    weight = weight.to(dev)
+    trow = torch.repeat_interleave(torch.arange(M, dtype=_I64, device=dev), boff[1:] - boff[:-1])
+    if bask.is_cuda:
+        if index is None:
+            index = recommend_index(ante_off, ante, F1)
+        rc = _native.hip().fa_hip_holdout_rank_combined(_p(index[0]), _p(index[1]), _p(ante_off), _p(ante),
+                                                        _p(cons), _p(weight), R, F1, _p(boff), _p(bask), _p(trow),
+                                                        T, n, _p(out), _stream(bask))
+        if rc == 2:  # the rows of one wave do not fit the LDS: host path
+            _combine_fallback("combined leave-one-out ranks", F1)
+            return holdout_rank_combined(ante_off.cpu(), ante.cpu(), cons.cpu(), weight.cpu(), F1, boff.cpu(),
+                                         bask.cpu(), n).to(dev)
+        _native.check(rc, "fa_hip_holdout_rank_combined")
+        return out
+    _native.host().fa_holdout_rank_combined_cpu(_p(ante_off), _p(ante), _p(cons), _p(weight), R, F1, _p(boff),
+                                                _p(bask), _p(trow), T, n, _p(out), num_threads())
+    return out
+
+
 def rules_build_device(levels: list, counts: list, tie_pos: np.ndarray, dev) -> dict:
     """Association rules on the GPU (csrc/hip/rules.hip; AssociationRules.scala:116-182).
 

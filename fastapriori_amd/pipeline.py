@@ -120,10 +120,13 @@ def recommend_window(cfg: JobConfig, comm, log: Logger, result, summary: dict) -
                                       ("write", t4 - t3))}
     if cfg.top_n > 0:
         # ranked lists next to the first-match file (no counterpart in the reference)
-        top = ar.run_topn(users, cfg.top_n, scores=cfg.top_n_scores)
+        # (--combine sum | votes: listed by the summed weights of all firing rules)
+        top = ar.run_topn(users, cfg.top_n, scores=cfg.top_n_scores, combine=cfg.combine)
         if comm.is_root:
             io.write_lines(top, cfg.output + "recommendsTopN", overwrite=cfg.overwrite)
             summary.update(top_n=cfg.top_n, n_topn_entries=sum(0 if l == "0" else l.count(" ") + 1 for l in top))
+        if cfg.combine != "first":
+            summary["combine"] = cfg.combine
         comm.barrier()
         summary["recommend_steps_ms"]["topn"] = round((time.perf_counter() - t4) * 1e3, 1)
     summary["n_rules"] = ar.rules().n_rules
@@ -143,7 +146,7 @@ def evaluate_window(cfg: JobConfig, comm, log: Logger, result, summary: dict) ->
     t0 = time.perf_counter()
     users = io.read_shard(cfg.input + "U.dat", comm)
     ar = AssociationRules(result, comm, Logger(comm.rank, enabled=False))
-    ev, lines = ar.run_evaluate(users, cfg.evaluate, rank_lines=cfg.evaluate_ranks)
+    ev, lines = ar.run_evaluate(users, cfg.evaluate, rank_lines=cfg.evaluate_ranks, combine=cfg.combine)
     for f in ar.stats.get("fallbacks", ()):
         log.metric(phase="fallback", what=f, stage="evaluate")
     err = None
@@ -159,9 +162,10 @@ def evaluate_window(cfg: JobConfig, comm, log: Logger, result, summary: dict) ->
         raise RuntimeError(f"--evaluate failed on rank 0: {err}")
     ms = int((time.perf_counter() - t0) * 1000)
     log.line(f"Total time for get evaluation {ms}")
+    mode = {"combine": ev.combine} if ev.combine != "first" else {}
     log.metric(phase="evaluate", n=ev.n, n_lines=ev.n_lines, n_lines_skipped=ev.n_lines_skipped,
-               n_trials=ev.n_trials, n_infrequent_tokens=ev.n_infrequent_tokens, hits=ev.hits, ms=ms)
-    summary.update(evaluate_n=ev.n, n_trials=ev.n_trials, hit_rate_at_n=ev.hit_rate[-1], mrr=ev.mrr)
+               n_trials=ev.n_trials, n_infrequent_tokens=ev.n_infrequent_tokens, hits=ev.hits, ms=ms, **mode)
+    summary.update(evaluate_n=ev.n, n_trials=ev.n_trials, hit_rate_at_n=ev.hit_rate[-1], mrr=ev.mrr, **mode)
 
 
 def count_window(cfg: JobConfig, comm, log: Logger, result, summary: dict) -> None:
