@@ -34,8 +34,32 @@ namespace fa {
 // the rounds' thresholds, in order (a function: host and device code both call it)
 constexpr int kRgNThr = 6;
 constexpr int rg_thr(int t) { return t == 0 ? 8 : t == 1 ? 6 : t == 2 ? 4 : t == 3 ? 3 : t == 4 ? 2 : 1; }
-// parent rows of a level the device step holds in LDS (three int32 counters per row)
+// parent rows of a level the device step regroups (its three counters per row are always in LDS)
 constexpr int kRgMaxRows = 12288;
+
+// LDS of the device step's rounds kernel (regroup.hip k_dl_rg_rounds), one workgroup per level:
+//   counters   u, u2, v: 16 bits per parent row each, two rows to a word (a parent has at most
+//              F1 - m <= kAgMaxF1 - 1 = 32,767 children, so a half never carries into the next)
+//   lists      the level's parent lists, uint16 [m + 1][C] (0xFFFF: not a row), and the
+//              unassigned candidates' indices, uint16 [C]
+// The counters always fit (kRgMaxRows).  The lists are in LDS when rg_lds_fits says so, else
+// the kernel reads them from its global scratch; the launcher sizes the launch and the
+// kernel picks its path by these same functions.
+constexpr int64_t kRgLdsMax = 160 * 1024 - 512;          // (minus the kernel's static scratch)
+constexpr int64_t rg_al16(int64_t b) { return (b + 15) & ~(int64_t)15; }
+constexpr int64_t rg_lds_counters(int64_t n) { return rg_al16(3 * 4 * ((n + 1) / 2)); }
+constexpr int64_t rg_lds_par(int64_t C, int64_t m) { return rg_al16(2 * C * (m + 1)); }
+constexpr int64_t rg_lds_all(int64_t n, int64_t C, int64_t m) {
+  return rg_lds_counters(n) + rg_lds_par(C, m) + rg_al16(2 * C);
+}
+// cap: the LDS bytes the step may use (at most kRgLdsMax)
+constexpr bool rg_lds_fits(int64_t n, int64_t C, int64_t m, int64_t cap) {
+  return C < 0xFFFF && rg_lds_all(n, C, m) <= cap;
+}
+constexpr int64_t rg_lds_bytes(int64_t n, int64_t C, int64_t m, int64_t cap) {
+  return rg_lds_fits(n, C, m, cap) ? rg_lds_all(n, C, m) : rg_lds_counters(n);
+}
+static_assert(rg_lds_counters(kRgMaxRows) <= kRgLdsMax, "the counters of any level fit");
 // The statistics of the bundle the post step last regrouped, in the control block (fa_dl.h:
 // slots free between kDlPiecesI32 and kDlBits): kRgStats + 4 l .. + 3 are level l's prefix
 // pieces, the rule's pieces, rounds, 1 = the level kept the prefix plan.

@@ -148,6 +148,9 @@ _HIP_SIGS = {
     "fa_hip_set_dl_regroup": (None, [C.c_int]),
     "fa_hip_dl_regroup_last": (None, [vp]),
     "fa_hip_dl_regroup_need": (i64, [vp, C.c_int]),
+    "fa_hip_set_dl_regroup_lds": (None, [i64]),
+    "fa_hip_dl_regroup_lds": (i64, [i64, i64, i64]),
+    "fa_hip_debug_dl_regroup_phases": (None, [vp]),
     "fa_hip_dl_regroup": (C.c_int, [vp, C.c_int, vp, i64, vp, vp, vp]),
     "fa_hip_dl_unpermute": (C.c_int, [vp, vp, i64, vp, vp]),
     "fa_hip_dl_gpre_need": (i64, [vp, C.c_int]),

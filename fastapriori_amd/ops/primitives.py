@@ -2297,13 +2297,15 @@ def lane_deal(lib, rows: int) -> None:
     lib.fa_hip_set_lane_deal(int(0 <= TUNING.lane_deal_min_rows <= rows))
 
 
-def dl_regroup(S: DeviceLevelState, L: int, dev) -> dict | None:
+def dl_regroup(S: DeviceLevelState, L: int, dev, lds_cap: int | None = None) -> dict | None:
     """The regrouping step on its own (regroup.hip fa_hip_dl_regroup; the miner reaches it inside
     the post step, gen.hip dl_post): S.desc[:L] regrouped.  Returns None when the bundle is not
     eligible (a prefix past kDlInline ids), else dict(desc: the regrouped level table for
     dl_plan(desc=...), perm: int32 [C] with perm[new bundle index] = the generator's, stats:
     int64 [L, 4] per level (the prefix plan's pieces, the rule's, rounds, 1 = kept the prefix
-    plan), scratch: the buffer desc points into)."""
+    plan), scratch: the buffer desc points into).  lds_cap (tests): the LDS bytes the rounds
+    kernel's fit rule may use in this call (fa_regroup.h rg_lds_fits; a level past it reads its
+    lists from global memory); the miner's own calls keep the device's."""
     lib = _native.hip()
     need = int(lib.fa_hip_dl_regroup_need(S.desc.ctypes.data, L))
     if need == 0:
@@ -2312,8 +2314,14 @@ def dl_regroup(S: DeviceLevelState, L: int, dev) -> dict | None:
     stats = torch.zeros((L, 4), dtype=_I64, device=dev)
     desc = S.desc.copy()
     st = torch.cuda.current_stream(dev).cuda_stream
-    _native.check(lib.fa_hip_dl_regroup(S.desc.ctypes.data, L, _p(scratch), need, desc.ctypes.data, _p(stats), st),
-                  "fa_hip_dl_regroup")
+    if lds_cap is not None:
+        lib.fa_hip_set_dl_regroup_lds(int(lds_cap))
+    try:
+        rc = lib.fa_hip_dl_regroup(S.desc.ctypes.data, L, _p(scratch), need, desc.ctypes.data, _p(stats), st)
+    finally:
+        if lds_cap is not None:
+            lib.fa_hip_set_dl_regroup_lds(-1)
+    _native.check(rc, "fa_hip_dl_regroup")
     C = int(S.desc["C"][:L].sum())
     perm = scratch[:4 * C].view(_I32)
     return dict(desc=desc, perm=perm, stats=stats, scratch=scratch)
