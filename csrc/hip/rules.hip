@@ -19,6 +19,7 @@
 // Host counterpart (same semantics, CPU runs and tests): csrc/host/rules.cpp.
 #include "fa_hip.h"
 #include "../host/fa_rule_measures.h"
+#include "../host/fa_rule_splits.h"
 
 namespace fa {
 
@@ -222,6 +223,135 @@ __global__ __launch_bounds__(kRuleTPB) void k_rm_emit(
   key[o] = rm_measure(sort, cS, cA, cC, N);
 }
 
+// ---------------------------------------------------------------------------
+// Rule export with multi-item consequents (all_rules(max_consequent = M); no counterpart in
+// the reference): every rule S \ B -> B of every frequent S, |S| = k >= 2, for every
+// non-empty proper subset B with |B| = b <= min(M, k - 1).  The enumeration -- element
+// numbering, unranking of a split into (b, position mask), the masked row compare -- is
+// ../host/fa_rule_splits.h, shared with rules.cpp fa_rule_splits_cpu.
+//
+// One thread per (itemset, split) element over all levels, an int64 index over eoff as
+// k_rm_count; the element total grows as 2^k per itemset, so NOTHING wider than one bit per
+// element lives between the passes:
+//   k_rs_count  unranks its split, finds S \ B in level k - b and B in level b, tests the
+//               thresholds, and stores one ballot word per wave and the workgroup's number
+//               of selected rules in wgtot (wg_sum);
+//   k_rm_scan   (above) the workgroup offsets, R into ctl[0];
+//   k_rs_emit   reads its wave's ballot word, ranks the selected lanes (wg_scan_excl) and
+//               redoes both searches for those only; placement as k_rm_emit: stable in
+//               enumeration order, no atomics.
+// Pascal rows 0 .. K and the n_k are staged in LDS once per workgroup (rs_stage); a mask's
+// items are read bit by bit from the row in global memory, which neighbouring lanes share.
+// ctl as k_rm_count: [1] = the largest level k with an antecedent or a consequent missing
+// from its level.  The ballot, the sums and the barriers sit outside every divergent branch.
+// ---------------------------------------------------------------------------
+__device__ const SplitPascal d_split_pascal{};
+
+struct RsAt {
+  int k, b;
+  uint32_t mask;           // positions of B in S
+  int64_t s;
+  const int32_t* row;      // S
+};
+
+// every thread of the workgroup calls it (it ends in a barrier); K <= kSplitMaxK
+__device__ __forceinline__ void rs_stage(uint32_t* pas, uint32_t* nk, int K, int M) {
+  for (int i = threadIdx.x; i < (K + 1) * kSplitStride; i += kRuleTPB) pas[i] = d_split_pascal.c[i];
+  if ((int)threadIdx.x <= K) nk[threadIdx.x] = split_count(d_split_pascal.c, (int)threadIdx.x, M);
+  __syncthreads();
+}
+
+__device__ __forceinline__ RsAt rs_locate(const int32_t* __restrict__ rows_all, const int64_t* __restrict__ base,
+                                          const int64_t* __restrict__ eoff, int K, const uint32_t* pas,
+                                          const uint32_t* nk, int64_t idx) {
+  // the last k in [2, K] with eoff[k] <= idx (an empty level has eoff[k] == eoff[k+1])
+  int klo = 2, khi = K;
+  while (klo < khi) {
+    const int mid = (klo + khi + 1) >> 1;
+    if (eoff[mid] <= idx) klo = mid; else khi = mid - 1;
+  }
+  RsAt a;
+  a.k = klo;
+  uint32_t j;
+  split_decode(idx - eoff[klo], nk[klo], &a.s, &j);
+  split_unrank(pas, klo, j, &a.b, &a.mask);
+  a.row = rows_all + base[klo] + a.s * klo;
+  return a;
+}
+
+// rows of S \ B in level k - b and of B in level b (-1: missing)
+__device__ __forceinline__ void rs_find(const int32_t* __restrict__ rows_all, const int64_t* __restrict__ base,
+                                        const int64_t* __restrict__ cbase, const RsAt& at, int64_t& fa, int64_t& fb) {
+  const int m = at.k - at.b;
+  fa = split_find(rows_all + base[m], cbase[m] - cbase[m - 1], m, at.row, split_full(at.k) & ~at.mask);
+  fb = split_find(rows_all + base[at.b], cbase[at.b] - cbase[at.b - 1], at.b, at.row, at.mask);
+}
+
+__global__ __launch_bounds__(kRuleTPB) void k_rs_count(
+    const int32_t* __restrict__ rows_all, const int64_t* __restrict__ base, const int64_t* __restrict__ cnt_all,
+    const int64_t* __restrict__ cbase, const int64_t* __restrict__ eoff, int K, int M, int64_t total, RuleSel q,
+    unsigned long long* __restrict__ ballots, int32_t* __restrict__ wgtot, unsigned long long* __restrict__ ctl) {
+  __shared__ uint32_t pas[kSplitStride * kSplitStride];
+  __shared__ uint32_t nk[kSplitStride];
+  __shared__ int scratch[kRmW];
+  rs_stage(pas, nk, K, M);
+  const int64_t idx = (int64_t)blockIdx.x * kRuleTPB + threadIdx.x;
+  int sel = 0;
+  if (idx < total) {
+    const RsAt at = rs_locate(rows_all, base, eoff, K, pas, nk, idx);
+    int64_t fa, fb;
+    rs_find(rows_all, base, cbase, at, fa, fb);
+    if (fa < 0 || fb < 0) {
+      atomicMax(ctl + 1, (unsigned long long)at.k);
+    } else {
+      sel = rm_selected(q, cnt_all[cbase[at.k - 1] + at.s], cnt_all[cbase[at.k - at.b - 1] + fa],
+                        cnt_all[cbase[at.b - 1] + fb]) ? 1 : 0;
+    }
+  }
+  const unsigned long long word = __ballot(sel);              // every lane reaches it
+  if (lane_id() == 0) ballots[(int64_t)blockIdx.x * kRmW + (threadIdx.x >> 6)] = word;
+  const int tot = wg_sum<kRmW>(sel, scratch);
+  if (threadIdx.x == 0) wgtot[blockIdx.x] = tot;
+}
+
+// R: the total k_rm_scan left in ctl[0] (the outputs hold R rules; nothing is written past it)
+__global__ __launch_bounds__(kRuleTPB) void k_rs_emit(
+    const int32_t* __restrict__ rows_all, const int64_t* __restrict__ base, const int64_t* __restrict__ cnt_all,
+    const int64_t* __restrict__ cbase, const int64_t* __restrict__ eoff, int K, int M, int64_t total, int64_t N,
+    int sort, const unsigned long long* __restrict__ ballots, const int64_t* __restrict__ wgoff, int64_t R,
+    int64_t* __restrict__ cntS, int64_t* __restrict__ cntA, int64_t* __restrict__ cntC, int32_t* __restrict__ asz,
+    int32_t* __restrict__ aidx, int32_t* __restrict__ csz, int32_t* __restrict__ cidx, double* __restrict__ conf,
+    double* __restrict__ key) {
+  __shared__ uint32_t pas[kSplitStride * kSplitStride];
+  __shared__ uint32_t nk[kSplitStride];
+  __shared__ int scratch[kRmW];
+  const int64_t idx = (int64_t)blockIdx.x * kRuleTPB + threadIdx.x;
+  const unsigned long long word = ballots[(int64_t)blockIdx.x * kRmW + (threadIdx.x >> 6)];
+  const int sel = (int)((word >> lane_id()) & 1ull);          // a lane past the total never selected
+  int wg_total;
+  const int before = wg_scan_excl<kRmW>(sel, scratch, wg_total);
+  if (wg_total == 0) return;                                  // the whole workgroup: before the barrier below
+  rs_stage(pas, nk, K, M);
+  if (!sel || idx >= total) return;
+  const int64_t o = wgoff[blockIdx.x] + before;
+  if (o >= R) return;
+  const RsAt at = rs_locate(rows_all, base, eoff, K, pas, nk, idx);
+  int64_t fa, fb;
+  rs_find(rows_all, base, cbase, at, fa, fb);                 // found by k_rs_count
+  if (fa < 0 || fb < 0) return;
+  const int64_t cS = cnt_all[cbase[at.k - 1] + at.s], cA = cnt_all[cbase[at.k - at.b - 1] + fa],
+                cC = cnt_all[cbase[at.b - 1] + fb];
+  cntS[o] = cS;
+  cntA[o] = cA;
+  cntC[o] = cC;
+  asz[o] = at.k - at.b;
+  aidx[o] = (int32_t)fa;
+  csz[o] = at.b;
+  cidx[o] = (int32_t)fb;
+  conf[o] = rm_confidence(cS, cA);
+  key[o] = rm_measure(sort, cS, cA, cC, N);
+}
+
 // the five measures of the kept rules, from their three counts (after the sort and the limit)
 __global__ __launch_bounds__(kRuleTPB) void k_rm_fin(
     const int64_t* __restrict__ cntS, const int64_t* __restrict__ cntA, const int64_t* __restrict__ cntC, int64_t R,
@@ -334,5 +464,50 @@ FA_API int fa_hip_rule_measures_fin(const int64_t* cntS, const int64_t* cntA, co
   if ((R + kRuleTPB - 1) / kRuleTPB >= (int64_t)INT32_MAX) return 3;
   hipLaunchKernelGGL(k_rm_fin, rule_grid(R), dim3(kRuleTPB), 0, st, cntS, cntA, cntC, R, N, support, conf, lift,
                      leverage, conviction);
+  FA_LAUNCH_RET();
+}
+
+// The multi-item-consequent export's selection and count: k_rs_count + k_rm_scan, whatever K
+// and M (consequents of up to M items; anything above K - 1 means every split).  Layout as
+// fa_hip_rule_measures with eoff[k] = the first (itemset, split) element of level k
+// (fa_rule_splits.h); ballots: one uint64 per wave of 64 elements, wgtot int32 and wgoff int64
+// per workgroup of 256, ctl two zeroed int64 words ([0] = R, [1] = error level on return).
+// 0 with no launch when no level above the first has a row; 3 for K > 32, M < 1, a level of
+// >= INT32_MAX rows or an element total whose grid does not fit (overflow-checked).
+FA_API int fa_hip_rule_splits(const int32_t* rows_all, const int64_t* base, const int64_t* cnt_all,
+                              const int64_t* cbase, const int64_t* eoff, const int64_t* sizes, int K, int M, int64_t N,
+                              double min_conf, int has_lift, double min_lift, int sort, uint64_t* ballots,
+                              int32_t* wgtot, int64_t* wgoff, int64_t* ctl, hipStream_t st) {
+  int64_t blocks = 0;
+  const int64_t total = split_total(kSplitPascal.c, sizes, K, M, kRuleTPB, &blocks, nullptr);
+  if (total < 0) return 3;
+  if (total == 0) return 0;
+  RuleSel q;
+  q.min_conf = min_conf;
+  q.min_lift = min_lift;
+  q.N = N;
+  q.has_lift = has_lift;
+  q.sort = sort;
+  hipLaunchKernelGGL(k_rs_count, dim3((unsigned)blocks), dim3(kRuleTPB), 0, st, rows_all, base, cnt_all, cbase, eoff,
+                     K, M, total, q, (unsigned long long*)ballots, wgtot, (unsigned long long*)ctl);
+  hipLaunchKernelGGL(k_rm_scan, dim3(1), dim3(kRmScanTPB), 0, st, wgtot, blocks, wgoff, (unsigned long long*)ctl);
+  FA_LAUNCH_RET();
+}
+
+// The R selected rules of fa_hip_rule_splits' ballots / wgoff, in enumeration order: their
+// three counts, the antecedent's size and row, the consequent's size and row (in level b; a
+// level-1 row is its item's), the confidence and the sort measure (R elements each).
+FA_API int fa_hip_rule_splits_emit(const int32_t* rows_all, const int64_t* base, const int64_t* cnt_all,
+                                   const int64_t* cbase, const int64_t* eoff, const int64_t* sizes, int K, int M,
+                                   int64_t N, int sort, const uint64_t* ballots, const int64_t* wgoff, int64_t R,
+                                   int64_t* cntS, int64_t* cntA, int64_t* cntC, int32_t* asz, int32_t* aidx,
+                                   int32_t* csz, int32_t* cidx, double* conf, double* key, hipStream_t st) {
+  int64_t blocks = 0;
+  const int64_t total = split_total(kSplitPascal.c, sizes, K, M, kRuleTPB, &blocks, nullptr);
+  if (total < 0) return 3;
+  if (total == 0 || R <= 0) return 0;
+  hipLaunchKernelGGL(k_rs_emit, dim3((unsigned)blocks), dim3(kRuleTPB), 0, st, rows_all, base, cnt_all, cbase, eoff,
+                     K, M, total, N, sort, (const unsigned long long*)ballots, wgoff, R, cntS, cntA, cntC, asz, aidx,
+                     csz, cidx, conf, key);
   FA_LAUNCH_RET();
 }

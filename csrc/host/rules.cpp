@@ -20,6 +20,7 @@
 #include "fa_combine.h"
 #include "fa_common.h"
 #include "fa_rule_measures.h"
+#include "fa_rule_splits.h"
 
 namespace fa {
 
@@ -616,3 +617,205 @@ FA_API void fa_rule_measures_export(RuleMeasureSet* h, int64_t* ante_off, int32_
 }
 
 FA_API void fa_rule_measures_free(RuleMeasureSet* h) { delete h; }
+
+// ---------------------------------------------------------------------------
+// Rule export with multi-item consequents (AssociationRules.all_rules(max_consequent = M); no
+// counterpart in the reference): every rule S \ B -> B of every frequent S, |S| = k >= 2, for
+// every non-empty proper subset B with |B| <= min(M, k - 1), with fa_rule_measures.h's
+// measures on cS = count(S), cA = count(S \ B) and cC = count(B).  The enumeration is
+// fa_rule_splits.h's.  Device counterpart (same inputs, selection, order and error):
+// csrc/hip/rules.hip k_rs_count / k_rm_scan / k_rs_emit / k_rm_fin.
+// ---------------------------------------------------------------------------
+namespace fa {
+
+struct RuleSplitSet {
+  std::vector<int64_t> ante_off, cons_off, cS, cA, cC;       // R+1, R+1, R, R, R
+  std::vector<int32_t> ante, cons;
+  std::vector<double> support, conf, lift, leverage, conviction;
+};
+
+}  // namespace fa
+
+// the enumeration by name, for the tests: n_k, the unranking (1: k, M or j out of range) and
+// the decode of a level-local index
+FA_API uint64_t fa_rule_split_count(int k, int M) {
+  return (k < 2 || k > kSplitMaxK || M < 1) ? 0 : (uint64_t)split_count(kSplitPascal.c, k, M);
+}
+FA_API int fa_rule_split_unrank(int k, int M, uint64_t j, int32_t* b, uint32_t* mask) {
+  if (j >= fa_rule_split_count(k, M)) return 1;
+  int bb;
+  split_unrank(kSplitPascal.c, k, (uint32_t)j, &bb, mask);
+  *b = bb;
+  return 0;
+}
+FA_API int fa_rule_split_decode(int64_t local, uint64_t nk, int64_t* s, uint64_t* j) {
+  if (local < 0 || nk == 0 || nk > 0xfffffffeull) return 1;
+  uint32_t jj;
+  split_decode(local, (uint32_t)nk, s, &jj);
+  *j = jj;
+  return 0;
+}
+
+// Layout, selection and limits as fa_rule_measures_cpu; M >= 1 caps the consequent's size
+// (anything above K - 1 means every split).  Order: the sort measure descending (+inf first),
+// confidence descending, consequent size, the consequent key (tie_pos[item] for one item,
+// else the consequent's row in its level), antecedent size, antecedent row -- a total order;
+// limit >= 0 keeps that many rules.  *n_rules: the rules kept, -k for the largest level k
+// with an antecedent or a consequent missing from its level, or INT64_MIN for K > 32, M < 1
+// or an element total past the device grid's (the caller checks all three first).
+FA_API RuleSplitSet* fa_rule_splits_cpu(const int32_t* rows_all, const int64_t* base, const int64_t* cnt_all,
+                                        const int64_t* cbase, int K, int M, int64_t N, double min_conf, int has_lift,
+                                        double min_lift, int sort, int64_t limit, const int64_t* tie_pos,
+                                        int nthreads, int64_t* n_rules) {
+  auto* out = new RuleSplitSet();
+  out->ante_off.push_back(0);
+  out->cons_off.push_back(0);
+  *n_rules = 0;
+  int levels = 0;
+  while (levels < K && cbase[levels + 1] > cbase[levels]) ++levels;
+  {
+    std::vector<int64_t> sizes((size_t)std::max(levels, 1), 0);
+    for (int k = 1; k <= levels; ++k) sizes[(size_t)k - 1] = cbase[k] - cbase[k - 1];
+    int64_t blocks = 0;
+    if (split_total(kSplitPascal.c, sizes.data(), levels, M, 256, &blocks, nullptr) < 0) {
+      *n_rules = INT64_MIN;
+      return out;
+    }
+  }
+  if (levels < 2) return out;
+  RuleSel q;
+  q.min_conf = min_conf;
+  q.min_lift = min_lift;
+  q.N = N;
+  q.has_lift = has_lift;
+  q.sort = sort;
+  const uint32_t* pas = kSplitPascal.c;
+  // elements in enumeration order, in chunks of about kChunk of them (whole itemsets): every
+  // chunk collects its selected rules, the chunks are joined in order
+  constexpr int64_t kChunk = 1 << 16;
+  struct Chunk { int k; int64_t s0, s1; };
+  std::vector<Chunk> chunks;
+  for (int k = 2; k <= levels; ++k) {
+    const int64_t nS = cbase[k] - cbase[k - 1];
+    const int64_t per = std::max<int64_t>(1, kChunk / (int64_t)split_count(pas, k, M));
+    for (int64_t s0 = 0; s0 < nS; s0 += per) chunks.push_back(Chunk{k, s0, std::min(nS, s0 + per)});
+  }
+  struct Sel { double key, conf; int64_t ckey, cS, cA, cC; int32_t csz, cidx, asz, aidx; };
+  std::vector<std::vector<Sel>> found(chunks.size());
+  std::atomic<int> bad{0};
+  parallel_for((int64_t)chunks.size(), nthreads, 1, [&](int64_t b0, int64_t e0, int) {
+    for (int64_t ci = b0; ci < e0; ++ci) {
+      const Chunk& c = chunks[(size_t)ci];
+      const int k = c.k;
+      const uint32_t nk = split_count(pas, k, M), full = split_full(k);
+      const int32_t* S = rows_all + base[k];
+      std::vector<Sel>& dst = found[(size_t)ci];
+      for (int64_t s = c.s0; s < c.s1; ++s) {
+        const int32_t* row = S + s * k;
+        const int64_t cS = cnt_all[cbase[k - 1] + s];
+        for (uint32_t j = 0; j < nk; ++j) {
+          int b;
+          uint32_t mask;
+          split_unrank(pas, k, j, &b, &mask);
+          const int m = k - b;
+          const int64_t fa = split_find(rows_all + base[m], cbase[m] - cbase[m - 1], m, row, full & ~mask);
+          const int64_t fb = split_find(rows_all + base[b], cbase[b] - cbase[b - 1], b, row, mask);
+          if (fa < 0 || fb < 0) {
+            int cur = bad.load(std::memory_order_relaxed);
+            while (cur < k && !bad.compare_exchange_weak(cur, k, std::memory_order_relaxed)) {}
+            continue;
+          }
+          const int64_t cA = cnt_all[cbase[m - 1] + fa], cC = cnt_all[cbase[b - 1] + fb];
+          if (!rm_selected(q, cS, cA, cC)) continue;
+          const int64_t ckey = b == 1 ? tie_pos[rows_all[base[1] + fb]] : fb;
+          dst.push_back(Sel{rm_measure(sort, cS, cA, cC, N), rm_confidence(cS, cA), ckey, cS, cA, cC, b, (int32_t)fb,
+                            m, (int32_t)fa});
+        }
+      }
+    }
+  });
+  if (bad.load()) {
+    *n_rules = -(int64_t)bad.load();
+    return out;
+  }
+  std::vector<int64_t> coff(chunks.size() + 1, 0);
+  for (size_t i = 0; i < chunks.size(); ++i) coff[i + 1] = coff[i] + (int64_t)found[i].size();
+  const int64_t R = coff[chunks.size()];
+  std::vector<Sel> sel((size_t)R);
+  parallel_for((int64_t)chunks.size(), nthreads, 1, [&](int64_t b0, int64_t e0, int) {
+    for (int64_t ci = b0; ci < e0; ++ci) {
+      std::copy(found[(size_t)ci].begin(), found[(size_t)ci].end(), sel.begin() + coff[(size_t)ci]);
+      std::vector<Sel>().swap(found[(size_t)ci]);
+    }
+  });
+  auto less = [](const Sel& x, const Sel& y) {
+    if (x.key != y.key) return x.key > y.key;
+    if (x.conf != y.conf) return x.conf > y.conf;
+    if (x.csz != y.csz) return x.csz < y.csz;
+    if (x.ckey != y.ckey) return x.ckey < y.ckey;
+    if (x.asz != y.asz) return x.asz < y.asz;
+    return x.aidx < y.aidx;
+  };
+  {
+    // sorted parts merged pairwise, as fa_rule_measures_cpu
+    const int T = (int)std::max<int64_t>(1, std::min<int64_t>(nthreads, R / 4096));
+    std::vector<int64_t> cut((size_t)T + 1);
+    for (int t = 0; t <= T; ++t) cut[t] = R * t / T;
+    parallel_for_threads(T, [&](int t) { std::sort(sel.begin() + cut[t], sel.begin() + cut[t + 1], less); });
+    for (int w = 1; w < T; w *= 2) {
+      const int nm = (T + 2 * w - 1) / (2 * w), nt = std::min(nm, std::max(nthreads, 1));
+      parallel_for_threads(nt, [&](int tid) {
+        for (int mi = tid; mi < nm; mi += nt) {
+          const int a0 = 2 * w * mi, a1 = std::min(T, a0 + w), a2 = std::min(T, a0 + 2 * w);
+          if (a1 < a2) std::inplace_merge(sel.begin() + cut[a0], sel.begin() + cut[a1], sel.begin() + cut[a2], less);
+        }
+      });
+    }
+  }
+  const int64_t keep = limit >= 0 ? std::min(limit, R) : R;
+  out->ante_off.resize((size_t)keep + 1);
+  out->cons_off.resize((size_t)keep + 1);
+  for (int64_t i = 0; i < keep; ++i) {
+    out->ante_off[(size_t)i + 1] = out->ante_off[(size_t)i] + sel[(size_t)i].asz;
+    out->cons_off[(size_t)i + 1] = out->cons_off[(size_t)i] + sel[(size_t)i].csz;
+  }
+  out->ante.resize((size_t)out->ante_off[(size_t)keep]);
+  out->cons.resize((size_t)out->cons_off[(size_t)keep]);
+  for (auto* v : {&out->cS, &out->cA, &out->cC}) v->resize((size_t)keep);
+  for (auto* v : {&out->support, &out->conf, &out->lift, &out->leverage, &out->conviction}) v->resize((size_t)keep);
+  parallel_for(keep, nthreads, 4096, [&](int64_t b0, int64_t e0, int) {
+    for (int64_t i = b0; i < e0; ++i) {
+      const Sel& r = sel[(size_t)i];
+      const int32_t* a = rows_all + base[r.asz] + (int64_t)r.aidx * r.asz;
+      const int32_t* c = rows_all + base[r.csz] + (int64_t)r.cidx * r.csz;
+      std::copy(a, a + r.asz, out->ante.begin() + out->ante_off[(size_t)i]);
+      std::copy(c, c + r.csz, out->cons.begin() + out->cons_off[(size_t)i]);
+      out->cS[i] = r.cS; out->cA[i] = r.cA; out->cC[i] = r.cC;
+      out->support[i] = rm_support(r.cS, N);
+      out->conf[i] = rm_confidence(r.cS, r.cA);
+      out->lift[i] = rm_lift(r.cS, r.cA, r.cC, N);
+      out->leverage[i] = rm_leverage(r.cS, r.cA, r.cC, N);
+      out->conviction[i] = rm_conviction(r.cS, r.cA, r.cC, N);
+    }
+  });
+  *n_rules = keep;
+  return out;
+}
+
+FA_API int64_t fa_rule_splits_nante(RuleSplitSet* h) { return (int64_t)h->ante.size(); }
+FA_API int64_t fa_rule_splits_ncons(RuleSplitSet* h) { return (int64_t)h->cons.size(); }
+
+// every array holds R elements (ante_off / cons_off R+1, ante / cons the two totals above)
+FA_API void fa_rule_splits_export(RuleSplitSet* h, int64_t* ante_off, int32_t* ante, int64_t* cons_off, int32_t* cons,
+                                  int64_t* cS, int64_t* cA, int64_t* cC, double* support, double* conf, double* lift,
+                                  double* leverage, double* conviction) {
+  auto put = [](auto* dst, const auto& v) {
+    if (!v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(v[0]));
+  };
+  put(ante_off, h->ante_off); put(ante, h->ante); put(cons_off, h->cons_off); put(cons, h->cons);
+  put(cS, h->cS); put(cA, h->cA); put(cC, h->cC);
+  put(support, h->support); put(conf, h->conf); put(lift, h->lift);
+  put(leverage, h->leverage); put(conviction, h->conviction);
+}
+
+FA_API void fa_rule_splits_free(RuleSplitSet* h) { delete h; }

@@ -252,3 +252,47 @@ FA_API int fa_write_rules(const char* path, const char* tokbuf, const int64_t* t
   const int rc = std::fclose(f);
   return (rc == 0 && ok) ? 0 : 2;
 }
+
+// fa_write_rules with field 2 generalised (all_rules(max_consequent >= 2)): the consequent's
+// tokens, rank-descending and one space apart, as the antecedent's.  A table of one-item
+// consequents gives fa_write_rules' bytes.
+FA_API int fa_write_rules_multi(const char* path, const char* tokbuf, const int64_t* tokoff, const int64_t* ante_off,
+                                const int32_t* ante, const int64_t* cons_off, const int32_t* cons, const int64_t* cS,
+                                const int64_t* cA, const int64_t* cC, const double* support, const double* conf,
+                                const double* lift, const double* leverage, const double* conviction, int64_t R,
+                                int nthreads) {
+  constexpr int64_t kChunk = 4096;
+  const int64_t nchunks = (R + kChunk - 1) / kChunk;
+  std::vector<std::string> text((size_t)nchunks);
+  auto tokens = [&](std::string& o, const int64_t* off, const int32_t* v, int64_t i) {
+    for (int64_t j = off[i + 1] - 1; j >= off[i]; --j) {               // ascending ranks: emit descending
+      o.append(tokbuf + tokoff[v[j]], (size_t)(tokoff[v[j] + 1] - tokoff[v[j]]));
+      if (j > off[i]) o.push_back(' ');
+    }
+  };
+  parallel_for(nchunks, nthreads, 1, [&](int64_t b, int64_t e, int) {
+    for (int64_t c = b; c < e; ++c) {
+      std::string& o = text[(size_t)c];
+      for (int64_t i = c * kChunk; i < std::min(R, (c + 1) * kChunk); ++i) {
+        tokens(o, ante_off, ante, i);
+        o.push_back('\t');
+        tokens(o, cons_off, cons, i);
+        for (const int64_t v : {cS[i], cA[i], cC[i]}) {
+          o.push_back('\t');
+          o += std::to_string((long long)v);
+        }
+        for (const double v : {support[i], conf[i], lift[i], leverage[i], conviction[i]}) {
+          o.push_back('\t');
+          repr_double(v, o);
+        }
+        o.push_back('\n');
+      }
+    }
+  });
+  FILE* f = std::fopen(path, "wb");
+  if (!f) return 1;
+  bool ok = true;
+  for (const std::string& t : text) ok = ok && (t.empty() || std::fwrite(t.data(), 1, t.size(), f) == t.size());
+  const int rc = std::fclose(f);
+  return (rc == 0 && ok) ? 0 : 2;
+}

@@ -91,6 +91,7 @@ class JobConfig:
     min_lift: float | None = None               # ... and lift >= this
     rules_sort: str = "confidence"              # ... ordered by this measure, descending
     rules_limit: int | None = None              # ... the first K only
+    rules_max_consequent: int = 1               # ... with consequents of up to M items (1: A -> c only)
     count_itemsets: str | None = None           # query file: also write <out>itemsetCounts ("a b[cnt]" per query line)
     count_only: bool = False                    # ... and end there: no mining, no U.dat, no checkpoint
     verify_counts: bool = False                 # recount every mined itemset of >= 2 items over D.dat and compare
@@ -155,6 +156,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--rules-sort", choices=list(RULE_SORTS), default=None,
                    help="with --rules: the measure the file is ordered by, descending (default confidence)")
     p.add_argument("--rules-limit", type=int, default=None, metavar="K", help="with --rules: the first K rules only")
+    p.add_argument("--rules-max-consequent", type=int, default=None, metavar="M",
+                   help="with --rules: also split every frequent itemset into 'A -> B' with B of up to M items "
+                        "(default 1: one-item consequents only; anything above the deepest level - 1 means every "
+                        "split). Field 2 then holds B's tokens one space apart, count(c) is count(B)")
     p.add_argument("--count-itemsets", metavar="PATH", default=None,
                    help="also write <output>itemsetCounts/: for every line of the query file PATH (tokenised as a "
                         "D.dat line; a blank line is the empty token) the number of D.dat lines that contain all of "
@@ -191,11 +196,14 @@ def parse_args(argv=None) -> JobConfig:
     if a.top_n_scores and not a.top_n:
         p.error("--top-n-scores requires --top-n")
     for flag, v in (("--min-confidence", a.min_confidence), ("--min-lift", a.min_lift),
-                    ("--rules-sort", a.rules_sort), ("--rules-limit", a.rules_limit)):
+                    ("--rules-sort", a.rules_sort), ("--rules-limit", a.rules_limit),
+                    ("--rules-max-consequent", a.rules_max_consequent)):
         if v is not None and not a.rules:
             p.error(f"{flag} requires --rules")
     if a.rules_limit is not None and a.rules_limit < 0:
         p.error(f"--rules-limit {a.rules_limit}: K must not be negative")
+    if a.rules_max_consequent is not None and a.rules_max_consequent < 1:
+        p.error(f"--rules-max-consequent {a.rules_max_consequent}: M must be at least 1")
     if a.count_only and not a.count_itemsets:
         p.error("--count-only requires --count-itemsets")
     for flag, on in (("--count-itemsets", a.count_itemsets), ("--count-only", a.count_only),
@@ -222,5 +230,6 @@ def parse_args(argv=None) -> JobConfig:
                      top_n_scores=a.top_n_scores, closed=a.closed, maximal=a.maximal, rules=a.rules,
                      min_confidence=0.0 if a.min_confidence is None else a.min_confidence, min_lift=a.min_lift,
                      rules_sort=a.rules_sort or "confidence", rules_limit=a.rules_limit,
+                     rules_max_consequent=a.rules_max_consequent or 1,
                      count_itemsets=a.count_itemsets, count_only=a.count_only, verify_counts=a.verify_counts,
                      evaluate=a.evaluate, evaluate_ranks=a.evaluate_ranks, combine=a.combine)

@@ -169,6 +169,48 @@ def all_rules(res: OracleResult, min_confidence: float = 0.0, min_lift: float | 
     return [t[:10] for t in (out if limit is None else out[:limit])]
 
 
+def rule_split_rows(res: OracleResult, max_consequent: int) -> list[tuple]:
+    """Every rule A -> B with S = A + B frequent, A and B non-empty and disjoint and
+    |B| <= max_consequent, unfiltered and unordered, as (A, B, cS, cA, cB, support, confidence,
+    lift, leverage, conviction, order tail) with frozensets and all_rules' arithmetic on
+    cB = count(B) (a one-item B: its occurrence count).  The order tail is (|B|, the
+    consequent key -- a one-item B's tiebreak position, else its ranks --, |A|, A's ranks)."""
+    n = res.n_lines
+    if n <= 0:
+        raise ValueError("all_rules: the line total is unknown")
+    if max_consequent < 1:
+        raise ValueError("all_rules: max_consequent must be at least 1")
+    tie = sorted(range(len(res.items)), key=lambda r: rule_tiebreak_key(res.items[r]))
+    tie_pos = {r: i for i, r in enumerate(tie)}
+    out = []
+    for s, cs in res.itemsets.items():
+        for b in range(1, min(max_consequent, len(s) - 1) + 1):
+            for cons in itertools.combinations(sorted(s), b):
+                bset = frozenset(cons)
+                a = s - bset
+                ca, cc = res.itemsets[a], res.itemsets[bset]
+                out.append((a, bset, cs, ca, cc, float(cs) / float(n), float(cs) / float(ca),
+                            float(cs * n) / float(ca * cc), float(cs * n - ca * cc) / float(n * n),
+                            float("inf") if ca == cs else float(ca * (n - cc)) / float(n * (ca - cs)),
+                            (b, (tie_pos[cons[0]],) if b == 1 else cons, len(a), tuple(sorted(a)))))
+    return out
+
+
+def all_rules_multi(res: OracleResult, max_consequent: int, min_confidence: float = 0.0,
+                    min_lift: float | None = None, sort: str = "confidence", limit: int | None = None,
+                    rows: list | None = None) -> list[tuple]:
+    """The rule export with multi-item consequents by brute force, NO cut, as (A, B, cS, cA,
+    cB, support, confidence, lift, leverage, conviction).  Kept: confidence >= min_confidence
+    and lift >= min_lift; order: the sort measure descending, confidence descending, then
+    rule_split_rows' order tail.  ``rows``: rule_split_rows(res, max_consequent), when the
+    caller has it already."""
+    col = {"support": 5, "confidence": 6, "lift": 7, "leverage": 8, "conviction": 9}[sort]
+    rows = rule_split_rows(res, max_consequent) if rows is None else rows
+    out = [t for t in rows if t[6] >= min_confidence and (min_lift is None or t[7] >= min_lift)]
+    out.sort(key=lambda t: (-t[col], -t[6], t[10]))
+    return [t[:10] for t in (out if limit is None else out[:limit])]
+
+
 def recommend(res: OracleResult, user_lines: list[list[str]]) -> list[str]:
     rules = sort_rules(gen_rules(res), res.items)
     rank = {t: i for i, t in enumerate(res.items)}

@@ -40,7 +40,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..ops.host import RuleMeasures, RuleTable, rule_measures, rules_build
+from ..ops.host import MultiRuleMeasures, RuleMeasures, RuleTable, rule_measures, rule_splits, rules_build
 from ..parallel.comm import Comm
 from ..utils.jvm import rule_tiebreak_key
 from ..utils.metrics import Logger
@@ -137,7 +137,7 @@ class AssociationRules:
         return self._rules
 
     def all_rules(self, min_confidence: float = 0.0, min_lift: float | None = None, sort: str = "confidence",
-                  limit: int | None = None) -> RuleMeasures:
+                  limit: int | None = None, max_consequent: int = 1) -> RuleMeasures | MultiRuleMeasures:
         """The rule export (an extension; the reference never shows its rules): EVERY rule
         A -> c with A + {c} frequent and at least two items -- the cut serves the recommender
         only and stays in rules() -- with support, confidence, lift, leverage and conviction
@@ -152,9 +152,27 @@ class AssociationRules:
         Takes the full mined result: a condensed one is not downward closed and raises
         RuntimeError, as any result with a subset missing from the level below; ValueError
         when the line total is unknown or it or a count exceeds 2^31 - 1.  A GPU rank
-        runs ops.primitives.rule_measures_device, a CPU rank ops.host.rule_measures."""
+        runs ops.primitives.rule_measures_device, a CPU rank ops.host.rule_measures.
+
+        ``max_consequent`` = M >= 2 splits every frequent S every way into A -> B with B of
+        at most M items (anything above the deepest level - 1: every split) and returns
+        MultiRuleMeasures: count(B) stands for count({c}) in the measures, and the order
+        gains the consequent's size in front of its key (a larger consequent's key is its row
+        in its level), so the one-item rules keep their relative order.  At most 32 levels;
+        ValueError for M < 1, for more levels and for an element total past one device grid
+        (docs/PARITY.md).  ops.primitives.rule_splits_device / ops.host.rule_splits."""
         r = self.result
         args = (min_confidence, min_lift, sort, limit)
+        if int(max_consequent) < 1:
+            raise ValueError(f"all_rules: max_consequent = {max_consequent} must be at least 1")
+        if int(max_consequent) >= 2:
+            if self.device.type == "cuda":
+                d = ops.primitives.rule_splits_device(r.levels, r.counts, r.n_lines, self._tie_pos(), self.device,
+                                                      *args, max_consequent)
+                return MultiRuleMeasures(*[d[k].cpu().numpy() for k in (
+                    "ante_off", "ante", "cons_off", "cons", "cnt_s", "cnt_a", "cnt_c", "support", "conf", "lift",
+                    "leverage", "conviction")])
+            return rule_splits(r.levels, r.counts, r.n_lines, self._tie_pos(), *args, max_consequent)
         if self.device.type == "cuda":
             d = ops.primitives.rule_measures_device(r.levels, r.counts, r.n_lines, self._tie_pos(), self.device, *args)
             return RuleMeasures(*[d[k].cpu().numpy() for k in ("ante_off", "ante", "cons", "cnt_s", "cnt_a", "cnt_c",

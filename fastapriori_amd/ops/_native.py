@@ -85,6 +85,17 @@ _HOST_SIGS = {
     "fa_rule_measures_export": (None, [vp] * 12),
     "fa_rule_measures_free": (None, [vp]),
     "fa_write_rules": (C.c_int, [cp, cp] + [vp] * 12 + [i64, C.c_int]),
+    # the export with multi-item consequents (rules.cpp) and its enumeration by name (csrc/host/fa_rule_splits.h)
+    "fa_rule_split_count": (u64, [C.c_int, C.c_int]),
+    "fa_rule_split_unrank": (C.c_int, [C.c_int, C.c_int, u64, vp, vp]),
+    "fa_rule_split_decode": (C.c_int, [i64, u64, vp, vp]),
+    "fa_rule_splits_cpu": (vp, [vp, vp, vp, vp, C.c_int, C.c_int, i64, dbl, C.c_int, dbl, C.c_int, i64, vp, C.c_int,
+                                vp]),
+    "fa_rule_splits_nante": (i64, [vp]),
+    "fa_rule_splits_ncons": (i64, [vp]),
+    "fa_rule_splits_export": (None, [vp] * 13),
+    "fa_rule_splits_free": (None, [vp]),
+    "fa_write_rules_multi": (C.c_int, [cp, cp] + [vp] * 13 + [i64, C.c_int]),
     "fa_recommend_cpu": (None, [vp, vp, vp, i64, i32, vp, vp, i64, vp, C.c_int]),
     "fa_recommend_topn_cpu": (None, [vp, vp, vp, i64, i32, vp, vp, i64, i32, vp, C.c_int]),
     "fa_holdout_rank_cpu": (None, [vp, vp, vp, i64, i32, vp, vp, vp, i64, i32, vp, C.c_int]),
@@ -204,6 +215,11 @@ _HIP_SIGS = {
     "fa_hip_rule_measures_emit": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, i64, C.c_int, vp, vp, i64, vp, vp, vp,
                                             vp, vp, vp, vp, vp, vp]),
     "fa_hip_rule_measures_fin": (C.c_int, [vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp]),
+    # ... with multi-item consequents (rules.hip k_rs_*): selection + count, emission
+    "fa_hip_rule_splits": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, i64, dbl, C.c_int, dbl, C.c_int, vp,
+                                     vp, vp, vp, vp]),
+    "fa_hip_rule_splits_emit": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, i64, C.c_int, vp, vp, i64] +
+                                [vp] * 10),
     "fa_hip_sup_mark": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]),
     # the query counter (query.hip k_query_slab): window descriptors on the host and on the device
     "fa_hip_query_count": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, i64, C.c_int, vp]),

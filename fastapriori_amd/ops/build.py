@@ -65,11 +65,12 @@ def _deps(kind: str) -> list[str]:
     if kind == "host":
         return host_sources() + sorted(glob.glob(os.path.join(CSRC, "host", "*.h")))
     # + the combined-scoring kernels' LDS rule, the slab rule, the device loop's contract, the
-    # kernels' limits, the query counter's and the exported rules' measures, which the kernels
-    # share with the host library (included by relative path)
+    # kernels' limits, the query counter's, the exported rules' measures and their split
+    # enumeration, which the kernels share with the host library (included by relative path)
     return hip_sources() + sorted(glob.glob(os.path.join(CSRC, "hip", "*.h"))) + [
         os.path.join(CSRC, "host", h) for h in ("fa_combine.h", "fa_dl.h", "fa_limits.h", "fa_query.h",
-                                                "fa_regroup.h", "fa_rule_measures.h", "fa_slab.h")]
+                                                "fa_regroup.h", "fa_rule_measures.h", "fa_rule_splits.h",
+                                                "fa_slab.h")]
 
 
 def source_id(kind: str, flags: list[str] | None = None) -> str:

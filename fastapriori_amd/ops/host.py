@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -118,7 +119,40 @@ class RuleMeasures:
         return self.ante[self.ante_off[i]:self.ante_off[i + 1]]
 
 
+@dataclass
+class MultiRuleMeasures:
+    """The exported rules with consequents of one or more items (AssociationRules.all_rules
+    with max_consequent >= 2): every rule A -> B of every frequent S = A + B, without the cut,
+    in the chosen order, with its three stored counts and five measures
+    (csrc/host/fa_rule_measures.h with count(B) for count({c}); a one-item B's count is its
+    occurrence count, a larger one's its line count)."""
+    ante_off: np.ndarray    # int64 [R+1]
+    ante: np.ndarray        # int32 concatenated antecedent ranks (ascending)
+    cons_off: np.ndarray    # int64 [R+1]
+    cons: np.ndarray        # int32 concatenated consequent ranks (ascending)
+    cnt_s: np.ndarray       # int64 [R] count(A + B)
+    cnt_a: np.ndarray       # int64 [R] count(A)
+    cnt_c: np.ndarray       # int64 [R] count(B)
+    support: np.ndarray     # float64 [R]
+    conf: np.ndarray        # float64 [R]
+    lift: np.ndarray        # float64 [R]
+    leverage: np.ndarray    # float64 [R]
+    conviction: np.ndarray  # float64 [R]
+
+    @property
+    def n_rules(self) -> int:
+        return int(self.cnt_s.size)
+
+    def antecedent(self, i: int) -> np.ndarray:
+        return self.ante[self.ante_off[i]:self.ante_off[i + 1]]
+
+    def consequent(self, i: int) -> np.ndarray:
+        return self.cons[self.cons_off[i]:self.cons_off[i + 1]]
+
+
 RULE_COUNT_MAX = 2 ** 31 - 1                                               # ... kRuleCountMax
+RULE_SPLIT_MAX_K = 32        # fa_rule_splits.h kSplitMaxK: a split's position mask is one uint32
+RULE_TPB = 256               # rules.hip kRuleTPB: elements per workgroup of the export
 
 
 def rule_measures_plan(levels, counts, n_lines, min_confidence, min_lift, sort, limit) -> dict:
@@ -198,6 +232,89 @@ def rule_measures(levels: list[np.ndarray], counts: list[np.ndarray], n_lines: i
     lib.fa_rule_measures_export(h, *[a.ctypes.data for a in (ante_off, ante, cons, *ints, *flts)])
     lib.fa_rule_measures_free(h)
     return RuleMeasures(ante_off, ante, cons, *ints, *flts)
+
+
+def rule_split_count(k: int, max_consequent: int) -> int:
+    """n_k of csrc/host/fa_rule_splits.h from Python ints: the splits of one k-itemset."""
+    return sum(math.comb(k, b) for b in range(1, min(max_consequent, k - 1) + 1))
+
+
+def rule_splits_plan(levels, counts, n_lines, min_confidence, min_lift, sort, limit, max_consequent=1,
+                     sizes=None) -> dict:
+    """What both paths of the export with multi-item consequents (rule_splits here,
+    ops.primitives.rule_splits_device) start from: rule_measures_plan's checks and layout,
+    plus M = max_consequent (ValueError below 1; anything above K - 1 means every split), the
+    level limit K <= 32 (ValueError) and eoff[k] = the first (itemset, split) element of level
+    k with the element total at eoff[K + 1], from Python ints.  A total that needs 2^31 - 1
+    workgroups of 256 or more raises ValueError before any native call.  ``sizes`` replaces
+    the levels' row counts in that last check (a plan for a result that is not in memory)."""
+    if int(max_consequent) < 1:
+        raise ValueError(f"all_rules: max_consequent = {max_consequent} must be at least 1")
+
+    def element_total(K, sz):
+        if K > RULE_SPLIT_MAX_K:
+            raise ValueError(f"all_rules: {K} levels exceed the limit of {RULE_SPLIT_MAX_K} on the max_consequent path "
+                             "(a split's position mask is one 32-bit word)")
+        M = max(1, min(int(max_consequent), K - 1))
+        eoff = [0] * (K + 2)
+        for k in range(2, K + 1):
+            eoff[k + 1] = eoff[k] + int(sz[k - 1]) * rule_split_count(k, M)
+        total = eoff[K + 1]
+        if (total + RULE_TPB - 1) // RULE_TPB >= 2 ** 31 - 1:
+            raise ValueError(f"all_rules: {total} (itemset, split) elements at max_consequent = {M} exceed the device "
+                             f"grid of 2^31 - 2 workgroups of {RULE_TPB}: use a smaller --rules-max-consequent or mine "
+                             "with --max-level")
+        return M, eoff
+
+    if sizes is not None:
+        K = 0
+        while K < len(sizes) and sizes[K] > 0:
+            K += 1
+        M, eoff = element_total(K, sizes)
+        return dict(K=K, M=M, eoff=np.array(eoff, dtype=np.int64))
+    m = rule_measures_plan(levels, counts, n_lines, min_confidence, min_lift, sort, limit)
+    m["M"], eoff = element_total(m["K"], m["sizes"])
+    m["eoff"] = np.array(eoff, dtype=np.int64)
+    return m
+
+
+def rule_splits(levels: list[np.ndarray], counts: list[np.ndarray], n_lines: int, tie_pos: np.ndarray,
+                min_confidence: float = 0.0, min_lift: float | None = None, sort: str = "confidence",
+                limit: int | None = None, max_consequent: int = 1) -> MultiRuleMeasures:
+    """The rule export with consequents of up to ``max_consequent`` items on the CPU
+    (csrc/host/rules.cpp fa_rule_splits_cpu): selection, order and errors as
+    ops.primitives.rule_splits_device; see rule_splits_plan.  max_consequent = 1 gives
+    rule_measures' rules with every consequent as a one-item list."""
+    m = rule_splits_plan(levels, counts, n_lines, min_confidence, min_lift, sort, limit, max_consequent)
+    tie = np.ascontiguousarray(tie_pos, dtype=np.int64)
+    if tie.size == 0:
+        tie = np.zeros(1, dtype=np.int64)
+    nr = np.zeros(1, dtype=np.int64)
+    lib = _native.host()
+    h = lib.fa_rule_splits_cpu(m["rows"].ctypes.data, m["base"].ctypes.data, m["cnts"].ctypes.data,
+                               m["cbase"].ctypes.data, m["K"], m["M"], m["N"], m["min_conf"], m["has_lift"],
+                               m["min_lift"], m["sort"], m["limit"], tie.ctypes.data, num_threads(), nr.ctypes.data)
+    R = int(nr[0])
+    if R < 0:
+        lib.fa_rule_splits_free(h)
+        if R == -2 ** 63:
+            raise RuntimeError("fa_rule_splits_cpu: the plan's limits do not hold")
+        raise splits_not_closed(-R)
+    na, nc = int(lib.fa_rule_splits_nante(h)), int(lib.fa_rule_splits_ncons(h))
+    ante_off, ante = np.zeros(R + 1, dtype=np.int64), np.zeros(na, dtype=np.int32)
+    cons_off, cons = np.zeros(R + 1, dtype=np.int64), np.zeros(nc, dtype=np.int32)
+    ints = [np.zeros(R, dtype=np.int64) for _ in range(3)]
+    flts = [np.zeros(R, dtype=np.float64) for _ in range(5)]
+    lib.fa_rule_splits_export(h, *[a.ctypes.data for a in (ante_off, ante, cons_off, cons, *ints, *flts)])
+    lib.fa_rule_splits_free(h)
+    return MultiRuleMeasures(ante_off, ante, cons_off, cons, *ints, *flts)
+
+
+def splits_not_closed(bad: int) -> RuntimeError:
+    """The error of both paths of the export with multi-item consequents for a result whose
+    level ``bad`` has an itemset with an antecedent or a consequent missing from its level."""
+    return RuntimeError(f"rules: an itemset of size {bad} has a subset that is not in the level of its size "
+                        "(the levels are not downward closed, or a level is not sorted)")
 
 
 def rules_not_closed(bad: int) -> RuntimeError:

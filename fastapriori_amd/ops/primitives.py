@@ -25,7 +25,7 @@ import torch
 from ..tuning import TUNING
 from ..utils.env import num_threads
 from . import _native
-from .host import rule_measures_plan, rules_gap_level, rules_not_closed
+from .host import rule_measures_plan, rule_splits_plan, rules_gap_level, rules_not_closed, splits_not_closed
 
 _I32, _I64 = torch.int32, torch.int64
 PAIR_CHUNK_ROWS = 1 << 18   # rows per pair-kernel chunk (working set ~10 MB: L2 / Infinity Cache resident)
@@ -1705,6 +1705,116 @@ def rule_measures_device(levels: list, counts: list, n_lines: int, tie_pos: np.n
     _native.check(lib.fa_hip_rule_emit(_p(rows_all), p_base, _p(msz_s), _p(idx_s), _p(ante_off), Rk, _p(ante), st),
                   "fa_hip_rule_emit")
     return result(ante_off, ante, cons[o].contiguous(), ints, flts)
+
+
+def rule_splits_device(levels: list, counts: list, n_lines: int, tie_pos: np.ndarray, dev,
+                       min_confidence: float = 0.0, min_lift: float | None = None, sort: str = "confidence",
+                       limit: int | None = None, max_consequent: int = 1) -> dict:
+    """The rule export with consequents of up to ``max_consequent`` items on the GPU
+    (csrc/hip/rules.hip k_rs_*; no counterpart in the reference): every rule S - B -> B of
+    every frequent S, |S| = k >= 2, for every non-empty proper subset B of at most
+    min(max_consequent, k - 1) items.
+
+    levels / counts as rule_measures_device, checked by ops.host.rule_splits_plan.  One
+    upload, then one dispatch sequence whatever the number of levels and max_consequent:
+    fa_hip_rule_splits selects and counts (one thread per (itemset, split) element over all
+    levels; one ballot bit per element and one total per workgroup are all that is kept),
+    the selected count R and the error word come back in ONE readback, and
+    fa_hip_rule_splits_emit writes only the R selected rules, stably and without atomics.
+    torch stable sorts order them (sort measure desc, confidence desc, consequent size, the
+    consequent key -- a one-item consequent's tie position, else its row in its level --
+    antecedent size, antecedent row: a total order), ``limit`` keeps a prefix,
+    fa_hip_rule_measures_fin writes the five measures and fa_hip_rule_emit gathers the
+    antecedents' and then the consequents' rows.  Returns tensors on ``dev``: ante_off /
+    cons_off int64 [R+1], ante / cons int32, cnt_s / cnt_a / cnt_c int64, support / conf /
+    lift / leverage / conviction float64.
+
+    An antecedent or a consequent missing from its level raises RuntimeError naming the
+    itemset's level through the error word, before anything is ordered."""
+    m = rule_splits_plan(levels, counts, n_lines, min_confidence, min_lift, sort, limit, max_consequent)
+    dev = torch.device(dev)
+    K, N, M = m["K"], m["N"], m["M"]
+    f64 = torch.float64
+
+    def result(ante_off, ante, cons_off, cons, ints, flts):
+        return dict(ante_off=ante_off, ante=ante, cons_off=cons_off, cons=cons, cnt_s=ints[0], cnt_a=ints[1],
+                    cnt_c=ints[2], support=flts[0], conf=flts[1], lift=flts[2], leverage=flts[3], conviction=flts[4])
+
+    def empty():
+        return result(torch.zeros(1, dtype=_I64, device=dev), torch.zeros(0, dtype=_I32, device=dev),
+                      torch.zeros(1, dtype=_I64, device=dev), torch.zeros(0, dtype=_I32, device=dev),
+                      [torch.zeros(0, dtype=_I64, device=dev) for _ in range(3)],
+                      [torch.zeros(0, dtype=f64, device=dev) for _ in range(5)])
+
+    total = int(m["eoff"][K + 1]) if K >= 2 else 0
+    nwg = (total + RULE_TPB - 1) // RULE_TPB
+    lib = _native.hip()
+    rows_all = torch.from_numpy(m["rows"]).to(dev)
+    n = m["n"]
+    tab = torch.from_numpy(np.concatenate([m["cnts"], m["base"], m["cbase"], m["eoff"]])).to(dev)
+    p0 = tab.data_ptr()
+    p_base, p_cbase, p_eoff = p0 + 8 * n, p0 + 8 * (n + K + 2), p0 + 8 * (n + 2 * K + 3)
+    st = _stream(rows_all)
+    ballots = torch.empty(max(nwg, 1) * (RULE_TPB // 64), dtype=_I64, device=dev)     # one bit per element
+    wgtot = torch.empty(max(nwg, 1), dtype=_I32, device=dev)
+    wgoff = torch.empty(max(nwg, 1), dtype=_I64, device=dev)
+    ctl = torch.zeros(2, dtype=_I64, device=dev)             # [0]: selected rules R, [1]: error level
+    rc = lib.fa_hip_rule_splits(_p(rows_all), p_base, p0, p_cbase, p_eoff, m["sizes"].ctypes.data, K, M, N,
+                                m["min_conf"], m["has_lift"], m["min_lift"], m["sort"], _p(ballots), _p(wgtot),
+                                _p(wgoff), _p(ctl), st)
+    if rc == 3:
+        raise RuntimeError("fa_hip_rule_splits: a level has 2^31 - 1 rows or more, or the (itemset, split) elements "
+                           "do not fit one grid")
+    _native.check(rc, "fa_hip_rule_splits")
+    if total == 0:
+        return empty()                                       # the launcher returned before any launch
+    R, bad = ctl.tolist()                                    # the one readback before the sort
+    if bad:
+        raise splits_not_closed(int(bad))
+    if R == 0:
+        return empty()
+    ints = [torch.empty(R, dtype=_I64, device=dev) for _ in range(3)]
+    asz, aidx, csz, cidx = (torch.empty(R, dtype=_I32, device=dev) for _ in range(4))
+    conf, key = torch.empty(R, dtype=f64, device=dev), torch.empty(R, dtype=f64, device=dev)
+    _native.check(lib.fa_hip_rule_splits_emit(_p(rows_all), p_base, p0, p_cbase, p_eoff, m["sizes"].ctypes.data, K, M,
+                                              N, m["sort"], _p(ballots), _p(wgoff), R, _p(ints[0]), _p(ints[1]),
+                                              _p(ints[2]), _p(asz), _p(aidx), _p(csz), _p(cidx), _p(conf), _p(key),
+                                              st), "fa_hip_rule_splits_emit")
+    del ballots
+    # the consequent key: a one-item consequent's tie position, else its row in its level
+    tie = torch.from_numpy(np.ascontiguousarray(tie_pos, dtype=np.int64)).to(dev)
+    l1 = rows_all[int(m["base"][1]):int(m["base"][2])].to(_I64)
+    one = csz == 1
+    ckey = torch.where(one, tie[l1[torch.where(one, cidx, torch.zeros_like(cidx)).to(_I64)]], cidx.to(_I64))
+    # total order, least significant key first: antecedent (size, row), consequent (size,
+    # key), confidence desc, the sort measure desc (+inf first)
+    o = torch.sort((asz.to(_I64) << 32) | aidx.to(_I64), stable=True)[1]
+    o = o[torch.sort(((csz.to(_I64) << 32) | ckey)[o], stable=True)[1]]
+    o = o[torch.sort(conf[o], descending=True, stable=True)[1]]
+    if m["sort"] != 0:
+        o = o[torch.sort(key[o], descending=True, stable=True)[1]]
+    if m["limit"] >= 0:
+        o = o[:m["limit"]]
+    Rk = int(o.numel())
+    if Rk == 0:
+        return empty()
+    ints = [c[o].contiguous() for c in ints]
+    flts = [torch.empty(Rk, dtype=f64, device=dev) for _ in range(5)]
+    _native.check(lib.fa_hip_rule_measures_fin(_p(ints[0]), _p(ints[1]), _p(ints[2]), Rk, N, *[_p(f) for f in flts],
+                                               st), "fa_hip_rule_measures_fin")
+
+    def gather(sz, idx):
+        sz_s, idx_s = sz[o].contiguous(), idx[o].contiguous()
+        off = torch.zeros(Rk + 1, dtype=_I64, device=dev)
+        torch.cumsum(sz_s.to(_I64), 0, out=off[1:])
+        out = torch.empty(int(off[-1].item()), dtype=_I32, device=dev)
+        _native.check(lib.fa_hip_rule_emit(_p(rows_all), p_base, _p(sz_s), _p(idx_s), _p(off), Rk, _p(out), st),
+                      "fa_hip_rule_emit")
+        return off, out
+
+    ante_off, ante = gather(asz, aidx)
+    cons_off, cons = gather(csz, cidx)
+    return result(ante_off, ante, cons_off, cons, ints, flts)
 
 
 def condense_marks(levels: list, counts: list, dev, check: bool = True) -> dict:

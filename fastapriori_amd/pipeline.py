@@ -261,14 +261,16 @@ def rules_window(cfg: JobConfig, comm, log: Logger, result, summary: dict) -> No
     """--rules (no counterpart in the reference): after condense_window and before the
     recommendation window, so neither of the reference's timed windows gets slower.  Every
     rank holds the identical result: rank 0 alone computes AssociationRules.all_rules on its
-    device and writes ``<output>rules`` (io.write_rules); the others meet it where it
+    device (with --rules-max-consequent M: consequents of up to M items) and writes
+    ``<output>rules`` (io.write_rules); the others meet it where it
     reports how that went, and a failure raises on every rank."""
     t0 = time.perf_counter()
     n, err = None, None
     if comm.is_root:
         try:
             ar = AssociationRules(result, comm, Logger(enabled=False))
-            rm = ar.all_rules(cfg.min_confidence, cfg.min_lift, cfg.rules_sort, cfg.rules_limit)
+            rm = ar.all_rules(cfg.min_confidence, cfg.min_lift, cfg.rules_sort, cfg.rules_limit,
+                              cfg.rules_max_consequent)
             io.write_rules(rm, result.items, cfg.output + "rules", overwrite=cfg.overwrite)
             n = rm.n_rules
         except (OSError, RuntimeError, ValueError) as e:
@@ -279,8 +281,9 @@ def rules_window(cfg: JobConfig, comm, log: Logger, result, summary: dict) -> No
     ms = int((time.perf_counter() - t0) * 1000)
     log.line(f"Total time for get rules {ms}")
     log.metric(phase="rules_export", n_rules=n, min_confidence=cfg.min_confidence, min_lift=cfg.min_lift,
-               sort=cfg.rules_sort, limit=cfg.rules_limit, ms=ms)
+               sort=cfg.rules_sort, limit=cfg.rules_limit, max_consequent=cfg.rules_max_consequent, ms=ms)
     summary["n_rules_exported"] = n
+    summary["rules_max_consequent"] = cfg.rules_max_consequent
 
 
 def make_checkpointer(cfg: JobConfig, comm) -> Checkpointer | None:

@@ -372,10 +372,24 @@ def write_rules(rules, items: list[str], out_dir: str, overwrite: bool = False) 
         cS <TAB> cA <TAB> cC <TAB> support <TAB> confidence <TAB> lift <TAB> leverage <TAB> conviction
 
     Floats are the shortest decimals that round-trip, byte-equal to Python's repr()
-    (``inf`` / ``-inf``); csrc/host/writer.cpp fa_write_rules."""
+    (``inf`` / ``-inf``); csrc/host/writer.cpp fa_write_rules.  An ops.host.MultiRuleMeasures
+    (consequents of one or more items) writes the consequent's tokens in field 2 as the
+    antecedent's in field 1 (fa_write_rules_multi); one-item consequents give the same bytes."""
     _prepare_dir(out_dir, overwrite)
     blob, off = _tokens_blob(items)
     part = os.path.join(out_dir, "part-00000")
+    if hasattr(rules, "cons_off"):
+        arrs = [np.ascontiguousarray(a, dtype=t) for a, t in
+                ((rules.ante_off, np.int64), (rules.ante, np.int32), (rules.cons_off, np.int64), (rules.cons, np.int32),
+                 (rules.cnt_s, np.int64), (rules.cnt_a, np.int64), (rules.cnt_c, np.int64), (rules.support, np.float64),
+                 (rules.conf, np.float64), (rules.lift, np.float64), (rules.leverage, np.float64),
+                 (rules.conviction, np.float64))]
+        rc = _native.host().fa_write_rules_multi(part.encode(), blob, off.ctypes.data, *[a.ctypes.data for a in arrs],
+                                                 rules.n_rules, num_threads())
+        if rc:
+            raise OSError(f"failed to write {part}")
+        open(os.path.join(out_dir, "_SUCCESS"), "wb").close()
+        return part
     arrs = [np.ascontiguousarray(a, dtype=t) for a, t in
             ((rules.ante_off, np.int64), (rules.ante, np.int32), (rules.cons, np.int32), (rules.cnt_s, np.int64),
              (rules.cnt_a, np.int64), (rules.cnt_c, np.int64), (rules.support, np.float64), (rules.conf, np.float64),
